@@ -1,8 +1,14 @@
 """Benchmark: agent-state stacks/s of the fused HIP observation path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--envs E | --total-envs T] [--gather R]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (the roofline figures in it come
+from those same K steps).  --full adds the legs that take runs of their own: the CPU baseline.
+--dump-outputs DIR writes the states the last timed step rendered (DIR/state.npy, float32; the
+scenes are seeded, so the same arguments give the same inputs run after run).
 
 Without a launcher, `--gpus N` (N > 1) starts N rank processes itself (one per GPU, before any GPU
 call in the parent); under a launcher, --gpus must equal its WORLD_SIZE.  More ranks than visible
@@ -207,6 +213,26 @@ def gather_states(out, reps, world, rank, return_data=False):
     return (stats, dst) if return_data else stats
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all ranks' files together stay below this
+
+
+def dump_outputs(dirname, out, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step -- this
+    rank's rendered states, float32 in the layout rendered -- as DIR/state.npy (DIR/state_rank<r>.npy
+    when several ranks run).  A block beyond this rank's share of DUMP_LIMIT_BYTES is cut to a
+    fixed, seeded sample of whole stacks, whose indices go to DIR/state_index[_rank<r>].npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    tag = '' if world == 1 else '_rank%d' % rank
+    a = out.detach().cpu().numpy()
+    keep = max(1, (DUMP_LIMIT_BYTES // world - 4096) // (a[0].nbytes + 8))
+    if a.shape[0] > keep:
+        idx = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+        np.save(os.path.join(dirname, 'state_index%s.npy' % tag), idx.astype(np.float64))
+        a = a[idx]
+    np.save(os.path.join(dirname, 'state%s.npy' % tag), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -313,6 +339,12 @@ def main(argv=None):
     ap.add_argument('--cpu-budget', type=float, default=6.0, help='seconds per CPU-baseline leg and worker')
     ap.add_argument('--cpu-procs', type=int, default=0, help='CPU-baseline processes (default: usable cores, capped)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what takes runs of its own beyond the timed steps: the CPU baseline (1 rank; '
+                         '--no-cpu-baseline still leaves it out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the states the last one rendered to DIR/state.npy (float32; '
+                         'a seeded sample of stacks beyond 64 MB)')
     ap.add_argument('--init-dist', action='store_true',
                     help='initialise the process group even for one rank (exercises the RCCL init / barrier / '
                          'all_reduce path on a 1-GPU box)')
@@ -380,6 +412,8 @@ def main(argv=None):
                              host=socket.gethostname(), env_range=[env_ids[0], env_ids[-1]],
                              stacks_per_step=b.N, steps=args.steps, seconds=own[0], kernel_ms=own_ms), world)
     ranks['launcher'] = launcher
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     stacks_per_step = int(sum_over_ranks([b.N], world, red)[0])
     value = stacks_per_step * args.steps / elapsed
@@ -424,7 +458,7 @@ def main(argv=None):
         res['distributed'] = ranks
         if gather is not None:
             res['gather'] = gather
-        if world == 1 and not args.no_cpu_baseline and not cpu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not cpu:
             res['cpu_baseline'] = cpu_baseline(args.config, args.cpu_budget, args.cpu_procs)
         print(json.dumps(res), flush=True)
     if dist_on:

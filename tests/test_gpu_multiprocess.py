@@ -61,6 +61,30 @@ def _worker(rank, world, port, total, out_dir):
 
 
 @pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_bench_dump_outputs_equals_direct_render(tmp_path, capsys):
+    """`bench.py --dump-outputs DIR` through the real main(): DIR/state.npy holds, bit for bit, the
+    states one direct render of the same seeded envs gives, and the line reports the steps asked for."""
+    import json
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from simaps import batch, synthetic
+    assert bench.main(['--gpus', '1', '--steps', '3', '--warmup', '1', '--envs', '3',
+                       '--dump-outputs', str(tmp_path)]) == 0
+    res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert res['steps'] == 3 and res['ms_per_step'] > 0 and 'cpu_baseline' not in res
+    got = np.load(os.path.join(tmp_path, 'state.npy'))
+    b = batch.StateBatch([synthetic.make_scene(CONFIG, e) for e in range(3)], device='cuda', layout='chw')
+    ref = b.alloc_state()
+    b.render(ref)
+    torch.cuda.synchronize()
+    ref = ref.cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == ref.shape == (12, res['config']['channels'], 96, 96)
+    assert np.array_equal(got.view(np.int32), ref.view(np.int32))
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(180)
 def test_two_ranks_shared_gpu_render_equals_unsharded(tmp_path):
     world, total = 2, 7

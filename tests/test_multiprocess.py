@@ -213,6 +213,45 @@ def test_bench_main_single_rank_line():
         assert res['distributed']['backend'] is None and res['distributed']['launcher'] == 'single'
 
 
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR writes what the last timed step rendered, float32 in the rendered layout,
+    after exactly --steps timed steps; --full is accepted and the line still carries ms_per_step."""
+    rc, lines, err = _run_bench(['--gpus', '1', '--standin', '--steps', '3', '--warmup', '1', '--envs', '2', '--full',
+                                 '--dump-outputs', str(tmp_path / 'dump')])
+    assert rc == 0, err
+    assert len(lines) == 1
+    res = lines[0]
+    assert res['steps'] == 3 and res['ms_per_step'] > 0
+    assert res['value'] == pytest.approx(res['config']['stacks_per_step'] * 1e3 / res['ms_per_step'])
+    assert sorted(os.listdir(tmp_path / 'dump')) == ['state.npy']
+    a = np.load(tmp_path / 'dump' / 'state.npy')
+    assert a.dtype == np.float32 and a.shape == (2 * 4, res['config']['channels'], 96, 96)
+    assert (a == 1.0).all()  # the stand-in's render
+
+
+def test_bench_dump_outputs_sample_is_fixed():
+    """A block beyond the size limit is cut to the same whole stacks every time, indices alongside."""
+    import tempfile
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.arange(40, dtype=torch.float32).reshape(10, 2, 2).contiguous()
+    limit, bench.DUMP_LIMIT_BYTES = bench.DUMP_LIMIT_BYTES, 4096 + 3 * (16 + 8)
+    try:
+        got = []
+        for _ in range(2):
+            with tempfile.TemporaryDirectory() as d:
+                bench.dump_outputs(d, out)
+                got.append((np.load(os.path.join(d, 'state.npy')), np.load(os.path.join(d, 'state_index.npy'))))
+    finally:
+        bench.DUMP_LIMIT_BYTES = limit
+    (a, ia), (b, ib) = got
+    assert a.shape == (3, 2, 2) and a.dtype == np.float32 and ia.dtype == np.float64
+    assert np.array_equal(a, b) and np.array_equal(ia, ib) and len(set(ia)) == 3
+    assert np.array_equal(a, out.numpy()[ia.astype(int)])
+
+
 def test_bench_refuses_mismatched_requests():
     """--gpus differing from a launcher's WORLD_SIZE, or more ranks than visible GPUs without
     --shared-gpu, exits non-zero with a message before any timed work."""

@@ -21,7 +21,7 @@ for step in "$@"; do
   case "$name" in
     pytest)  c="600|python -u -m pytest ${extra:-tests} -m gpu -x -q --timeout 120 --timeout-method thread"; extra="" ;;
     smoke)   c="120|python -c 'import __graft_entry__ as g; g.smoke()'" ;;
-    bench)   c="300|python bench.py" ;;
+    bench)   c="300|python bench.py --full" ;;
     bench20) c="200|python bench.py --gpus 1 --steps 20 --warmup 5" ;;
     prof)    c="600|bash tools/profile_round.sh $tag" ;;
     configs) c="400|bash tools/bench_configs.sh" ;;
