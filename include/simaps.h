@@ -5,8 +5,10 @@
  * are HIP device allocations (e.g. torch CUDA/ROCm tensors' data_ptr()).  `stream` is a
  * hipStream_t passed as void* (NULL = default stream); every compute call is asynchronous on it.
  * Return value: 0 = ok, negative = error (see SIMAPS_E*; simaps_last_error() has the text).
- * No exceptions cross the ABI.  Thread-safe: no global mutable state besides the last-error
- * string (thread-local) and the process-wide device fault word (simaps_fault_status).
+ * No exceptions cross the ABI.  The last-error string is thread-local.  The entry points here run
+ * on the process-wide DEFAULT context: one device fault word (simaps_fault_status) and one path mode
+ * (simaps_path_mode) shared by every thread and device of the process.  simaps_ctx.h has the scoped
+ * form: contexts that each own a fault record, a path mode and a memory pool.
  *
  * Reference interfaces replaced (file:line relative to the reference repo root):
  *   simaps_get_state    <- Mapper.get_state (envs.py:2068-2185) for a batch of agents, including
@@ -48,11 +50,12 @@ extern "C" {
 #define SIMAPS_EHIP -3        /* HIP runtime error (launch / memory) */
 #define SIMAPS_EDEVICE -4     /* an earlier launch reported a device-side fault (simaps_fault_status) */
 
-/* Device-side fault bits (simaps_fault_status).  Every kernel of this library ORs them into one
- * process-wide host-mapped word when a workgroup hits a condition that makes its output invalid;
- * never set in a correct run.  The next simaps_get_state / simaps_sp_distance /
- * simaps_shortest_path / simaps_sssp_grid call returns SIMAPS_EDEVICE (and clears the word) if it
- * is set, so a fault surfaces even when no debug buffers were passed. */
+/* Device-side fault bits (simaps_fault_status).  Every kernel launched through this header ORs them
+ * into the default context's host-mapped word -- one for the whole process -- when a workgroup hits
+ * a condition that makes its output invalid; never set in a correct run.  The next compute call of
+ * this header returns SIMAPS_EDEVICE (and clears the word) if it is set, so a fault surfaces even
+ * when no debug buffers were passed.  Launches through a context of simaps_ctx.h post into that
+ * context's own record instead, which also says which kernel and which agent / query posted. */
 #define SIMAPS_FAULT_TIMEOUT 1u    /* a wave-group barrier or scratch hand-over gave up waiting (~0.1 s) */
 #define SIMAPS_FAULT_ROUNDS 2u     /* the SSSP round cap was hit (no convergence) */
 #define SIMAPS_FAULT_DESCRIPTOR 4u /* a descriptor field outside this build's limits was clamped: num_robots

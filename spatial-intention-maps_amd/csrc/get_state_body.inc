@@ -219,7 +219,7 @@
     }
     if (tid == 0) {
         const unsigned f = group_faults(sh.bar, sh.rounds, nsrc);
-        post_faults(fault, f);
+        post_faults(fault, f, GS_MIXED ? SIMAPS_K_GET_STATE_MIXED : SIMAPS_K_GET_STATE, n);
         if (dbg.status) {
             int st = (f & SIMAPS_FAULT_ROUNDS ? 2 : 0) | (f & SIMAPS_FAULT_TIMEOUT ? 4 : 0) |
                      (f & SIMAPS_FAULT_DESCRIPTOR ? 8 : 0);

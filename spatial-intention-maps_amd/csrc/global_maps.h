@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(NT) global_maps_kernel(simaps_config cfg, Geom
     if (tid == 0) {
         sh.nr = nr;
         sh.me = ag.robot;
-        if (bad) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR);
+        if (bad) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GLOBAL_MAPS, n);
     }
     if (tid < nr) robot_params(sh.rob[tid], rb[tid], cfg, geo, H, W);
     if (tid >= 128 && tid < 128 + 5 * 24) sh.mwin[tid - 128] = geo.mbits[(tid - 128) / 24][(tid - 128) % 24];

@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(GL_NT) gl_sssp_kernel(int H, int W, const uint
             }
         }
     }
-    if (tid == 0) post_faults(fault, f);
+    if (tid == 0) post_faults(fault, f, SIMAPS_K_GL_SSSP, b);
     if (!out) return;
     float *o = out + (long)b * H * W;
     for (long k = tid; k < (long)H * W; k += GL_NT) {
@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(GT_NT) gl_tile_kernel(int H, int W, const uint
     const bool s_in = si >= wi0 && si < wi0 + wh && sj >= wj0 && sj < wj0 + ww && grid[(long)si * W + sj] != 0;
     const int ntj = (ww + GT_TT - 1) / GT_TT, nt = gt_tiles(wh, ww);
     if (nt > GT_MAXT) {  // (the host dispatches such windows to gl_sssp_kernel: a guard for the LDS tables)
-        if (tid == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR);
+        if (tid == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GL_TILE, b);
         return;
     }
     // (rows by wave, columns by lane: no 64-bit index division; four independent loads in flight per
@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(GT_NT) gl_tile_kernel(int H, int W, const uint
         unsigned f = ab == 1u ? SIMAPS_FAULT_ROUNDS : ab ? SIMAPS_FAULT_TIMEOUT : 0u;
         for (int q = 0; q < GT_GROUPS; q++)
             if (sh.bar[q][2]) f |= SIMAPS_FAULT_TIMEOUT;
-        post_faults(fault, f);
+        post_faults(fault, f, SIMAPS_K_GL_TILE, b);
     }
     if (!out) return;
     for (int i = tid >> 6; i < H; i += GT_NT / 64) {
@@ -835,5 +835,5 @@ __global__ void __launch_bounds__(64) gl_path_kernel(int H, int W, const uint8_t
         }
         if (lane == 0) out_n[b] = cnt_out;
     }
-    if (lane == 0) post_faults(fault, fault_bits);
+    if (lane == 0) post_faults(fault, fault_bits, SIMAPS_K_GL_PATH, b);
 }

@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(PNT) occupancy_map_kernel(simaps_config cfg, G
     build_cspace<PNT>(S, nullptr, hd.h, hd.w, rad, g, nullptr, 0, nullptr, occupancy + (size_t)ag.map_slot * H * W, H,
                       W, hd.i0, hd.j0);  // (ends with a sync: S.freeb and S.win are complete)
     if (chunk == 0) {
-        if (tid == 0 && bad) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR);
+        if (tid == 0 && bad) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_OCCUPANCY_MAP, n);
         const size_t base = (size_t)n * H * W;
         for (int i = wave; i < H; i += PNT / 64) {  // a wave per row, a lane per column
             const int r = i - hd.i0;

@@ -46,7 +46,7 @@
 
 #include "geom.h"
 #include "mixed.h"
-#include "simaps.h"
+#include "simaps_ctx.h"  // (includes simaps.h)
 
 using namespace simaps;
 
@@ -219,22 +219,29 @@ __device__ __forceinline__ Group whole_wg() { return Group{(int)threadIdx.x, 102
 constexpr int SIMAPS_NFAULT = 3;  // SIMAPS_FAULT_* bits
 
 // Always-on fault reporting (include/simaps.h SIMAPS_FAULT_*): one thread per workgroup, after the
-// kernel's last LDS barrier, ORs the conditions that invalidate its output into the process-wide
-// host-mapped fault word.  `desc` holds SIMAPS_FAULT_DESCRIPTOR if a descriptor was clamped.
+// kernel's last LDS barrier, ORs the conditions that invalidate its output into the host-mapped
+// fault record of the context the launch came through (`fault`; the process-wide one for simaps.h's
+// entry points).  `desc` holds SIMAPS_FAULT_DESCRIPTOR if a descriptor was clamped.
 __device__ __forceinline__ unsigned group_faults(const unsigned (&bar)[4][4], int rounds, int nsrc)
 {
     unsigned f = (bar[0][2] | bar[1][2] | bar[2][2] | bar[3][2]) ? SIMAPS_FAULT_TIMEOUT : 0u;
     if (nsrc > 0 && rounds >= (1 << 20)) f |= SIMAPS_FAULT_ROUNDS;
     return f | (bar[0][3] ? SIMAPS_FAULT_DESCRIPTOR : 0u);
 }
-__device__ __forceinline__ void post_faults(unsigned *fault, unsigned f)
+constexpr int SIMAPS_WHERE = 3;  // word of the fault record that says where a fault was posted
+__device__ __forceinline__ void post_faults(unsigned *fault, unsigned f, unsigned kernel_id, unsigned unit)
 {
     // fault[k] = 1 for bit k: plain system-scope vector stores into fine-grained host memory (no
     // PCIe atomics needed; concurrent writers store the same value); only in a faulting workgroup,
-    // i.e. never in a correct run
-    if (fault)
+    // i.e. never in a correct run.  Before the flags, where: (SIMAPS_K_* << 24) | the unit of the
+    // call's batch dimension (include/simaps_ctx.h), one 32-bit store of the same kind, which cannot
+    // tear -- if several workgroups fault, any one of them wins.
+    if (fault && f) {
+        __hip_atomic_store(fault + SIMAPS_WHERE, (kernel_id << 24) | min(unit, 0xFFFFFFu), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
         for (int k = 0; k < SIMAPS_NFAULT; k++)
             if (f & (1u << k)) __hip_atomic_store(fault + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 // A workgroup's own LDS fault word: waves that do not meet at a barrier (the overlapped path kernel's
 // SPFA wave beside its sweep waves) may set bits at the same time, so every writer ORs atomically.
@@ -2538,7 +2545,7 @@ __global__ void __launch_bounds__(NT) sssp_grid_kernel(int H, int W, const uint8
     }
     lds_barrier();
     sssp(sh, S, dist, 1);
-    if (tid == 0) post_faults(fault, group_faults(sh.bar, sh.rounds, 1));
+    if (tid == 0) post_faults(fault, group_faults(sh.bar, sh.rounds, 1), SIMAPS_K_SSSP_GRID, b);
     // A blocked source has no edges but still dist 0 (pyx:84-88 set dists[source] before the loop).
     const int src_k = sh.src_s[0][0] * W + sh.src_s[0][1];
     for (int k = tid; k < H * W; k += NT) {
@@ -2609,7 +2616,9 @@ __global__ void __launch_bounds__(NT) sp_distance_kernel(simaps_config cfg, Geom
     snap_sources(sh, S, 1, whole_wg());
     const bool src_ok = sh.src_ok[0];
     sssp(sh, S, dist, 1);  // the source's distance image (GridGraph._spfa_with_cache, pyx:116-119)
-    if (tid == 0) post_faults(fault, group_faults(sh.bar, sh.rounds, 1) | (sh.flag[1] ? SIMAPS_FAULT_DESCRIPTOR : 0u));
+    if (tid == 0)
+        post_faults(fault, group_faults(sh.bar, sh.rounds, 1) | (sh.flag[1] ? SIMAPS_FAULT_DESCRIPTOR : 0u),
+                    SIMAPS_K_SP_DISTANCE, n);
     if (rec_cache)  // the source is the receptacle (the caller's contract): keep the array for simaps_sp_lookup
         rec_export(rec_cache + (size_t)ag.map_slot * rec_cache_bytes(sh.h, sh.w), dist, sh.h, sh.w, src_ok, S.freeb, tid, NT);
     const int pw = sssp_pitch(sh.w);
@@ -3571,7 +3580,7 @@ __global__ void __launch_bounds__(PNT) path_kernel(simaps_config cfg, Geometry g
     if (sh.flag[0]) {
         if (tid == 0) {
             o[0] = sx; o[1] = sy; o[2] = tx; o[3] = ty; out_n[n] = 2;
-            post_faults(fault, sh.fault);
+            post_faults(fault, sh.fault, SIMAPS_K_PATH, n);
         }
         return;
     }
@@ -3598,7 +3607,7 @@ __global__ void __launch_bounds__(PNT) path_kernel(simaps_config cfg, Geometry g
             }
             if (lane == 0) out_n[n] = cnt;
         }
-        if (lane == 0) post_faults(fault, sh.fault);
+        if (lane == 0) post_faults(fault, sh.fault, SIMAPS_K_PATH, n);
     }
 }
 
@@ -3660,7 +3669,7 @@ __global__ void __launch_bounds__(PNT) grid_path_kernel(int H, int W, const uint
             }
             if (lane == 0) out_n[b] = cnt;
         }
-        if (lane == 0) post_faults(fault, sh.fault);
+        if (lane == 0) post_faults(fault, sh.fault, SIMAPS_K_GRID_PATH, b);
     }
 }
 
@@ -3808,11 +3817,13 @@ __device__ __forceinline__ int wave_reduce_dpp(int v, bool is_min)
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int pk_min_u16(int a, int b)
 {
-    return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+    return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2,
+                              b)));
 }
 __device__ __forceinline__ int pk_max_u16(int a, int b)
 {
-    return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+    return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2,
+                              b)));
 }
 
 // np.floor(v).astype(np.int32) then np.clip(., 0, n - 1) (envs.py:2440-2442) of an already floored
@@ -4102,6 +4113,7 @@ __global__ void __launch_bounds__(INGEST_RES_WG) ingest_resolve_kernel(
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <new>
 #include <vector>
 
 namespace {
@@ -4116,51 +4128,128 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-// The process-wide device fault word (include/simaps.h SIMAPS_FAULT_*): SIMAPS_NFAULT flags in
-// fine-grained (coherent) host memory that every device can write without a copy, read by the next
-// compute call without synchronising.  Allocated on first use; never freed (process lifetime).
-std::once_flag g_fault_once;
-volatile unsigned *g_fault_host = nullptr;
-unsigned *g_fault_dev = nullptr;
+// A context (include/simaps_ctx.h): the state that is per process in include/simaps.h.  The entry
+// points of simaps.h run on the process-wide default context (device -1: the calling thread's current
+// device, one fault record for all devices, one pool per device ordinal); a created context is bound
+// to one device and uses only that ordinal's pool slot.
+}  // namespace
 
-unsigned *fault_word()
+struct simaps_ctx {
+    int device = -1;
+    // The fault record (SIMAPS_FAULT_*): SIMAPS_NFAULT flags and the `where` word in 64 bytes of
+    // fine-grained (coherent) host memory that every device can write without a copy, read by the
+    // context's next compute call without synchronising.  Allocated on first use; the default
+    // context's is never freed (process lifetime).
+    std::once_flag fault_once;
+    volatile unsigned *fault_host = nullptr;
+    unsigned *fault_dev = nullptr;
+    std::atomic<int> path_mode{0};  // simaps_path_mode
+    std::once_flag pool_once[64];   // the private memory pool of each device ordinal (pool_alloc)
+    hipMemPool_t pool[64] = {};
+};
+
+namespace {
+simaps_ctx g_default_ctx;
+
+// live created contexts: every handle that comes through the ABI is looked up here
+std::mutex g_ctx_mu;
+std::vector<simaps_ctx *> g_ctx_live;
+
+// NULL -> the default context; a live handle -> itself; anything else -> nullptr (and the error text)
+simaps_ctx *resolve_ctx(const simaps_ctx *h)
 {
-    std::call_once(g_fault_once, [] {
+    if (!h) return &g_default_ctx;
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        for (simaps_ctx *c : g_ctx_live)
+            if (c == h) return c;
+    }
+    fail(SIMAPS_EINVAL, "context handle %p is not a live context (never created, or already destroyed)", (const void *)h);
+    return nullptr;
+}
+
+// A call through a created context runs on the context's device: switch the calling thread to it
+// if another device is current, and back on every return path.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(const simaps_ctx &cx)
+    {
+        if (cx.device < 0) return;  // the default context: the current device, as it is
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess) ok = false;
+        else if (cur != cx.device) {
+            if (hipSetDevice(cx.device) != hipSuccess) ok = false;
+            else prev = cur;
+        }
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+unsigned *fault_word(simaps_ctx &cx)
+{
+    std::call_once(cx.fault_once, [&cx] {
         void *h = nullptr;
         if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess)
             return;
         memset(h, 0, 64);
         void *d = nullptr;
         if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) return;
-        g_fault_host = static_cast<volatile unsigned *>(h);
-        g_fault_dev = static_cast<unsigned *>(d);
+        cx.fault_host = static_cast<volatile unsigned *>(h);
+        cx.fault_dev = static_cast<unsigned *>(d);
     });
-    return g_fault_dev;
+    return cx.fault_dev;
 }
 
-unsigned read_faults(bool clear)
+// the flag bits, and (where != nullptr) the `where` word a faulting workgroup stored before them
+unsigned read_faults(simaps_ctx &cx, bool clear, unsigned *where = nullptr)
 {
     unsigned f = 0;
-    if (!g_fault_host) return 0;
+    if (where) *where = 0;
+    if (!cx.fault_host) return 0;
     for (int k = 0; k < SIMAPS_NFAULT; k++) {
         // clear with an exchange: a fault posted by a launch still in flight between a read and a
         // separate store of 0 would be erased unreported
-        const unsigned v = clear ? __atomic_exchange_n(&g_fault_host[k], 0u, __ATOMIC_ACQ_REL)
-                                 : __atomic_load_n(&g_fault_host[k], __ATOMIC_ACQUIRE);
+        const unsigned v = clear ? __atomic_exchange_n(&cx.fault_host[k], 0u, __ATOMIC_ACQ_REL)
+                                 : __atomic_load_n(&cx.fault_host[k], __ATOMIC_ACQUIRE);
         if (v) f |= 1u << k;
     }
+    const unsigned w = clear ? __atomic_exchange_n(&cx.fault_host[SIMAPS_WHERE], 0u, __ATOMIC_ACQ_REL)
+                             : __atomic_load_n(&cx.fault_host[SIMAPS_WHERE], __ATOMIC_ACQUIRE);
+    if (where) *where = w;
     return f;
 }
 
-// Entry check of every compute call: a fault posted by an earlier launch fails this call (once).
-int pending_faults()
+// SIMAPS_K_* -> the kernel's name (simaps/_lib.py K_NAMES mirrors it)
+const char *kernel_name(unsigned id)
 {
-    if (!fault_word()) return fail(SIMAPS_EHIP, "could not allocate the host-mapped fault word");
-    const unsigned f = read_faults(true);
+    static const char *const names[SIMAPS_K_COUNT + 1] = {
+        "?", "get_state", "get_state_mixed", "sp_distance", "path", "sssp_grid", "grid_path", "gl_sssp", "gl_tile",
+        "gl_path", "occupancy_map", "global_maps"};
+    return id <= SIMAPS_K_COUNT ? names[id] : "?";
+}
+
+// Entry check of every compute call: a fault posted by an earlier launch through this context fails
+// this call (once).  The default context's message is the one simaps.h always gave; a created
+// context's also says where, when that is known.
+int pending_faults(simaps_ctx &cx)
+{
+    if (!fault_word(cx)) return fail(SIMAPS_EHIP, "could not allocate the host-mapped fault word");
+    unsigned where = 0;
+    const unsigned f = read_faults(cx, true, &where);
     if (!f) return 0;
-    return fail(SIMAPS_EDEVICE, "an earlier launch reported device fault bits 0x%x (%s%s%s): its outputs are invalid", f,
+    char tail[64] = "";
+    if (cx.device >= 0 && where)
+        snprintf(tail, sizeof(tail), " in %s, unit %u", kernel_name(where >> 24), where & 0xFFFFFFu);
+    return fail(SIMAPS_EDEVICE,
+                "an earlier launch reported device fault bits 0x%x (%s%s%s): its outputs are invalid%s", f,
                 f & SIMAPS_FAULT_TIMEOUT ? "barrier timeout " : "", f & SIMAPS_FAULT_ROUNDS ? "SSSP round cap " : "",
-                f & SIMAPS_FAULT_DESCRIPTOR ? "descriptor clamped" : "");
+                f & SIMAPS_FAULT_DESCRIPTOR ? "descriptor clamped" : "", tail);
 }
 
 // Robot geometry with the reference's own expressions (envs.py:802-810, 1060, 1280, 2218-2242, 2421).
@@ -4211,7 +4300,7 @@ const Geometry &geometry()
     return g;
 }
 
-// Path kernel choice (simaps_path_mode).  1: compact.  2: early exit (the SSSP fixpoint first, then the
+// Path kernel choice (simaps_path_mode, per context).  1: compact.  2: early exit (the SSSP fixpoint first, then the
 // SPFA only until the target's parent chain is final; same LDS footprint and pop loop as compact, so it
 // pays its sweeps, ~15 us small rooms / ~26 us large, and chain checks: measured 0.7-1.05x the compact
 // launch time for targets across the room and 0.5-0.95x for targets in the robot's local map, DESIGN.md
@@ -4219,7 +4308,6 @@ const Geometry &geometry()
 // fixpoint in LDS -- no pool scratch, so graph capture keeps it -- at 2 small-room / 1 large-room
 // queries per CU instead of 4 / 2).  0, automatic: OVL while the launch is resident at once at OVL's
 // residency (N <= CUs x per-CU), else 2 (compact when the launch is being captured).
-std::atomic<int> g_path_mode{0};
 enum PathKind { PK_COMPACT, PK_EARLY, PK_OVL };
 int device_cus()
 {
@@ -4233,9 +4321,9 @@ int device_cus()
     }
     return v;
 }
-PathKind path_kind(int n, bool small)
+PathKind path_kind(const simaps_ctx &cx, int n, bool small)
 {
-    switch (g_path_mode.load()) {
+    switch (cx.path_mode.load()) {
     case 1: return PK_COMPACT;
     case 2: return PK_EARLY;
     case 3: return PK_OVL;
@@ -4249,7 +4337,7 @@ PathKind path_kind(int n, bool small)
 // ordered, taken from a private memory pool of the device right before the launch
 // (hipMallocFromPoolAsync on the launch stream) and handed back right after it (hipFreeAsync on the
 // same stream), so no buffer is ever shared between launches, threads or streams, and nothing is
-// synchronised.  The pool is this library's own (created once per device, release threshold 256 MiB so
+// synchronised.  The pool is the context's own (created once per context and device, release threshold 256 MiB so
 // it keeps the path scratch: after the first launches this is a pool hit); the device's default pool,
 // which other libraries in the process allocate from, is left as it was.  A launch being captured into
 // a graph gets none and takes the compact kernels (same results) instead.
@@ -4264,9 +4352,7 @@ struct PathScratch {
         if (p) (void)hipFreeAsync(p, st);  // ordered after the launch that uses it
     }
 };
-std::once_flag g_pool_once[64];
-hipMemPool_t g_pool[64] = {};
-bool pool_alloc(PathScratch &ps, hipStream_t st, size_t bytes)
+bool pool_alloc(simaps_ctx &cx, PathScratch &ps, hipStream_t st, size_t bytes)
 {
     int dev = 0;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -4276,7 +4362,7 @@ bool pool_alloc(PathScratch &ps, hipStream_t st, size_t bytes)
     // An error left pending by the caller stays pending for the launch's own check: no scratch then
     // (the compact kernels run), and nothing here clears it.
     if (hipPeekAtLastError() != hipSuccess) return false;
-    std::call_once(g_pool_once[dev], [dev] {
+    std::call_once(cx.pool_once[dev], [&cx, dev] {
         hipMemPoolProps props = {};
         props.allocType = hipMemAllocationTypePinned;
         props.handleTypes = hipMemHandleTypeNone;
@@ -4293,11 +4379,11 @@ bool pool_alloc(PathScratch &ps, hipStream_t st, size_t bytes)
         // to the device at the next synchronisation instead of staying reserved for the process.
         uint64_t keep = 256ull << 20;
         (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-        g_pool[dev] = pool;
+        cx.pool[dev] = pool;
     });
-    if (!g_pool[dev]) return false;
+    if (!cx.pool[dev]) return false;
     void *p = nullptr;
-    if (hipMallocFromPoolAsync(&p, bytes, g_pool[dev], st) != hipSuccess) {
+    if (hipMallocFromPoolAsync(&p, bytes, cx.pool[dev], st) != hipSuccess) {
         (void)hipGetLastError();  // (only this call's error)
         return false;
     }
@@ -4306,7 +4392,7 @@ bool pool_alloc(PathScratch &ps, hipStream_t st, size_t bytes)
     return true;
 }
 // the early-exit path kernels' scratch: none (the compact kernels run instead) when it cannot be had
-void path_scratch(PathScratch &ps, hipStream_t st, size_t bytes) { (void)pool_alloc(ps, st, bytes); }
+void path_scratch(simaps_ctx &cx, PathScratch &ps, hipStream_t st, size_t bytes) { (void)pool_alloc(cx, ps, st, bytes); }
 
 // the LDS-resident GridGraph kernels' window limit (include/simaps.h); beyond it grid_large.h
 bool window_fits_lds(int wh, int ww)
@@ -4323,14 +4409,14 @@ bool gl_tiled(int wh, int ww) { return SIMAPS_GL_TILE && (long)gt_tiles(wh, ww) 
 
 // scratch of the large-window GridGraph kernels (stream-ordered, the library's pool); they have no
 // other path, so a launch being captured into a graph is refused instead
-int large_scratch(PathScratch &ps, hipStream_t st, size_t bytes, const char *what)
+int large_scratch(simaps_ctx &cx, PathScratch &ps, hipStream_t st, size_t bytes, const char *what)
 {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) return fail(SIMAPS_EHIP, "hipStreamIsCapturing failed");
     if (cap != hipStreamCaptureStatusNone)
         return fail(SIMAPS_EUNSUPPORTED, "%s on a window beyond the LDS-resident limit cannot be captured into a graph "
                     "(its scratch is taken in stream order per launch)", what);
-    if (!pool_alloc(ps, st, bytes)) return fail(SIMAPS_EHIP, "%s: no device scratch of %zu bytes", what, bytes);
+    if (!pool_alloc(cx, ps, st, bytes)) return fail(SIMAPS_EHIP, "%s: no device scratch of %zu bytes", what, bytes);
     return 0;
 }
 
@@ -4373,11 +4459,7 @@ int simaps_debug_read_stamps(unsigned long long *host_out)
 
 const char *simaps_last_error(void) { return g_err; }
 
-int simaps_fault_status(int clear)
-{
-    if (!fault_word()) return fail(SIMAPS_EHIP, "could not allocate the host-mapped fault word");
-    return (int)read_faults(clear != 0);
-}
+int simaps_fault_status(int clear) { return simaps_ctx_fault_status(nullptr, clear); }
 
 int simaps_num_channels(const simaps_config *c, int num_robots)
 {
@@ -4459,7 +4541,8 @@ int simaps_robot_mask(int type, int with_cube, float *out)
     return 0;
 }
 
-int simaps_get_state(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                          const simaps_env *envs,
                      const simaps_robot *robots, const double *paths, const uint8_t *occupancy, const float *overhead,
                      float *state, int num_robots_per_env, const simaps_debug *dbg, void *stream)
 {
@@ -4475,7 +4558,7 @@ int simaps_get_state(const simaps_config *cfg, int N, const simaps_agent *agents
     if (cfg->use_intention_channels && (num_robots_per_env < 1 || num_robots_per_env > SIMAPS_MAX_ROBOTS))
         return fail(SIMAPS_EINVAL, "intention channels need num_robots_per_env in [1, %d]", SIMAPS_MAX_ROBOTS);
     const int C = simaps_num_channels(cfg, num_robots_per_env > 0 ? num_robots_per_env : 1);
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     simaps_debug d;
     memset(&d, 0, sizeof(d));
     if (dbg) d = *dbg;
@@ -4484,17 +4567,18 @@ int simaps_get_state(const simaps_config *cfg, int N, const simaps_agent *agents
         hipFuncSetAttribute((const void *)get_state_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (lds_ok != hipSuccess) return fail(SIMAPS_EHIP, "dynamic LDS of the VGPR-cap build");
     hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), LDS_BYTES, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, state, C, d, g_fault_dev);
+                       robots, paths, occupancy, overhead, state, C, d, cx.fault_dev);
 #else
     hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, state, C, d, g_fault_dev);
+                       robots, paths, occupancy, overhead, state, C, d, cx.fault_dev);
 #endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
     return 0;
 }
 
-int simaps_get_state_mixed(const simaps_config *cfgs, const int32_t *num_robots_per_env, int n_cfgs, int N,
+static int get_state_mixed_impl(simaps_ctx &cx, const simaps_config *cfgs, const int32_t *num_robots_per_env,
+                                int n_cfgs, int N,
                            const simaps_agent *agents, const int32_t *agent_cfg, const simaps_env *envs,
                            const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
                            const int64_t *map_off, const float *overhead, float *state, const int64_t *out_off,
@@ -4524,9 +4608,9 @@ int simaps_get_state_mixed(const simaps_config *cfgs, const int32_t *num_robots_
     if (!agents || !agent_cfg || !envs || !robots || !occupancy || !map_off || !overhead || !state || !out_off)
         return fail(SIMAPS_EINVAL, "NULL buffer");
     if (any_paths && !paths) return fail(SIMAPS_EINVAL, "paths is NULL");
-    if (const int rc = pending_faults()) return rc;
+    if (const int rc = pending_faults(cx)) return rc;
     simaps_mixed::launch_get_state_mixed(mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off, overhead,
-                                         state, out_off, g_fault_dev, (hipStream_t)stream);
+                                         state, out_off, cx.fault_dev, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_mixed launch: %s", hipGetErrorString(e));
     return 0;
@@ -4539,7 +4623,8 @@ int simaps_rec_cache_bytes(const simaps_config *cfg)
     return rec_cache_bytes(cfg->room_h, cfg->room_w);
 }
 
-int simaps_sp_lookup(const simaps_config *cfg, int N, const simaps_agent *agents, const void *rec_cache,
+static int sp_lookup_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                          const void *rec_cache,
                      const double *targets, int Q, double *out, void *stream)
 {
     int rc = check_cfg(cfg);
@@ -4547,7 +4632,7 @@ int simaps_sp_lookup(const simaps_config *cfg, int N, const simaps_agent *agents
     if (N < 0 || Q < 0) return fail(SIMAPS_EINVAL, "N < 0 or Q < 0");
     if (N == 0 || Q == 0) return 0;
     if (!agents || !rec_cache || !targets || !out) return fail(SIMAPS_EINVAL, "NULL buffer");
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     hipLaunchKernelGGL(sp_lookup_kernel, dim3(N), dim3(LNT), 0, (hipStream_t)stream, *cfg, agents,
                        reinterpret_cast<const char *>(rec_cache), rec_cache_bytes(cfg->room_h, cfg->room_w), targets, Q, out);
     const hipError_t e = hipGetLastError();
@@ -4555,7 +4640,8 @@ int simaps_sp_lookup(const simaps_config *cfg, int N, const simaps_agent *agents
     return 0;
 }
 
-int simaps_sp_distance(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int sp_distance_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                            const simaps_env *envs,
                        const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
                        const double *targets, int Q, double *out, void *rec_cache, void *stream)
 {
@@ -4565,16 +4651,17 @@ int simaps_sp_distance(const simaps_config *cfg, int N, const simaps_agent *agen
     if (N == 0 || Q == 0) return 0;
     if (!agents || !envs || !robots || !occupancy || !sources || !targets || !out)
         return fail(SIMAPS_EINVAL, "NULL buffer");
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     const Geometry &geo = geometry();
     hipLaunchKernelGGL(sp_distance_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geo, agents, envs, robots,
-                       occupancy, sources, targets, Q, out, reinterpret_cast<char *>(rec_cache), g_fault_dev);
+                       occupancy, sources, targets, Q, out, reinterpret_cast<char *>(rec_cache), cx.fault_dev);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "sp_distance launch: %s", hipGetErrorString(e));
     return 0;
 }
 
-int simaps_shortest_path(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int shortest_path_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                              const simaps_env *envs,
                          const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
                          const double *targets, int max_points, double *out_xy, int32_t *out_count, void *stream)
 {
@@ -4584,17 +4671,17 @@ int simaps_shortest_path(const simaps_config *cfg, int N, const simaps_agent *ag
     if (N == 0) return 0;
     if (!agents || !envs || !robots || !occupancy || !sources || !targets || !out_xy || !out_count)
         return fail(SIMAPS_EINVAL, "NULL buffer");
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     const Geometry &geo = geometry();
     const bool small = (cfg->room_h + 2) * ((cfg->room_w + 2) | 1) <= PATH_SMALL_CELLS;
     const hipStream_t st = (hipStream_t)stream;
-    const PathKind kind = path_kind(N, small);
+    const PathKind kind = path_kind(cx, N, small);
     PathScratch ps;
-    if (kind == PK_EARLY) path_scratch(ps, st, (size_t)N * SIMAPS_MAX_ROOM_CELLS * sizeof(float));
+    if (kind == PK_EARLY) path_scratch(cx, ps, st, (size_t)N * SIMAPS_MAX_ROOM_CELLS * sizeof(float));
     float *scratch = ps.p;
 #define SIMAPS_PATH_LAUNCH(C, E, O)                                                                    \
     hipLaunchKernelGGL((path_kernel<C, E, O>), dim3(N), dim3(PNT), 0, st, *cfg, geo, agents, envs, robots, occupancy, \
-                       sources, targets, max_points, out_xy, out_count, scratch, g_fault_dev)
+                       sources, targets, max_points, out_xy, out_count, scratch, cx.fault_dev)
     if (kind == PK_OVL) {
         if (small) SIMAPS_PATH_LAUNCH(PATH_SMALL_CELLS, true, true);
         else SIMAPS_PATH_LAUNCH(SIMAPS_MAX_ROOM_CELLS, true, true);
@@ -4611,11 +4698,7 @@ int simaps_shortest_path(const simaps_config *cfg, int N, const simaps_agent *ag
     return 0;
 }
 
-int simaps_path_mode(int mode)
-{
-    if (mode < 0 || mode > 3) return fail(SIMAPS_EINVAL, "path mode %d not in 0..3", mode);
-    return g_path_mode.exchange(mode);
-}
+int simaps_path_mode(int mode) { return simaps_ctx_path_mode(nullptr, mode); }
 
 int simaps_ingest_chunks(int height_px, int width_px)
 {
@@ -4623,7 +4706,8 @@ int simaps_ingest_chunks(int height_px, int width_px)
     return ingest_chunks(height_px, width_px);
 }
 
-int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, const simaps_agent *agents,
+static int ingest_impl(simaps_ctx &cx, const simaps_config *cfg, const simaps_camera *cam, int N,
+                       const simaps_agent *agents,
                   const simaps_seg_ids *seg_ids, const double *cam_params, const float *depth, const int32_t *seg_raw,
                   float *overhead, uint8_t *occupancy, uint64_t *keys, uint32_t *boxes, int epoch, void *stream)
 {
@@ -4637,7 +4721,8 @@ int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, con
         return fail(SIMAPS_EINVAL, "NULL buffer");
     const int np = cam->height_px * cam->width_px;
     if (!ingest_width_ok(cam->width_px))
-        return fail(SIMAPS_EUNSUPPORTED, "camera width %d outside [%d, %d]", cam->width_px, ingest_min_width(), INGEST_MAX_WC);
+        return fail(SIMAPS_EUNSUPPORTED, "camera width %d outside [%d, %d]", cam->width_px, ingest_min_width(),
+                    INGEST_MAX_WC);
     if (np >= (1 << 20)) return fail(SIMAPS_EUNSUPPORTED, "camera frame of %d pixels (key packs pixel + 1 in 20 bits)", np);
     if (epoch < 0 || epoch > 255) return fail(SIMAPS_EINVAL, "epoch %d not in [0, 255]", epoch);
     {   // a captured launch replays its epoch: only the zeroing mode (epoch 0) leaves nothing behind
@@ -4652,7 +4737,7 @@ int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, con
     if (zero_mode) epoch = 1;
     if (N > 65535) return fail(SIMAPS_EUNSUPPORTED, "%d frames per launch (grid y <= 65535)", N);
     const int nch = ingest_chunks(cam->height_px, cam->width_px);  // point-pass chunks per frame
-    if ((rc = pending_faults())) return rc;  // (after the argument checks: they need no device)
+    if ((rc = pending_faults(cx))) return rc;  // (after the argument checks: they need no device)
     if (cam->width_px + INGEST_PPT <= 320)
         hipLaunchKernelGGL(ingest_points_kernel<320>, dim3(nch, N), dim3(INGEST_WG), 0, (hipStream_t)stream, *cfg, *cam, agents,
                            seg_ids, cam_params, depth, seg_raw, occupancy, reinterpret_cast<unsigned long long *>(keys), boxes, (unsigned)epoch);
@@ -4670,7 +4755,8 @@ int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, con
     return 0;
 }
 
-int simaps_grid_path(int B, int H, int W, const uint8_t *grids, const int32_t *sources, const int32_t *targets,
+static int grid_path_impl(simaps_ctx &cx, int B, int H, int W, const uint8_t *grids, const int32_t *sources,
+                          const int32_t *targets,
                      int wi0, int wj0, int wh, int ww, int max_points, int32_t *out_ij, int32_t *out_count, void *stream)
 {
     if (B < 0 || H <= 0 || W <= 0 || max_points < 1) return fail(SIMAPS_EINVAL, "bad batch / grid shape / max_points");
@@ -4681,31 +4767,31 @@ int simaps_grid_path(int B, int H, int W, const uint8_t *grids, const int32_t *s
         return fail(SIMAPS_EINVAL, "window outside the grid");
     const hipStream_t st = (hipStream_t)stream;
     if (!window_fits_lds(wh, ww)) {  // any larger window: the global-memory kernels (grid_large.h)
-        if (const int rc = pending_faults()) return rc;
+        if (const int rc = pending_faults(cx)) return rc;
         const long words = gl_path_words(wh, ww);
         PathScratch ps;
-        if (const int rc = large_scratch(ps, st, (size_t)B * words * sizeof(int), "grid_path")) return rc;
+        if (const int rc = large_scratch(cx, ps, st, (size_t)B * words * sizeof(int), "grid_path")) return rc;
         if (gl_tiled(wh, ww))
             hipLaunchKernelGGL(gl_tile_kernel, dim3(B), dim3(GT_NT), 0, st, H, W, grids, (long)H * W, sources, wi0, wj0, wh,
-                               ww, ps.p, words, nullptr, g_fault_dev);
+                               ww, ps.p, words, nullptr, cx.fault_dev);
         else
             hipLaunchKernelGGL(gl_sssp_kernel, dim3(B), dim3(GL_NT), 0, st, H, W, grids, (long)H * W, sources, wi0, wj0, wh,
-                               ww, ps.p, words, nullptr, g_fault_dev);
+                               ww, ps.p, words, nullptr, cx.fault_dev);
         hipLaunchKernelGGL(gl_path_kernel, dim3(B), dim3(64), 0, st, H, W, grids, (long)H * W, sources, targets, wi0, wj0,
-                           wh, ww, reinterpret_cast<int *>(ps.p), words, max_points, out_ij, out_count, g_fault_dev);
+                           wh, ww, reinterpret_cast<int *>(ps.p), words, max_points, out_ij, out_count, cx.fault_dev);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(SIMAPS_EHIP, "grid_path (large window) launch: %s", hipGetErrorString(e));
         return 0;
     }
-    if (const int rc = pending_faults()) return rc;
+    if (const int rc = pending_faults(cx)) return rc;
     const bool small = (wh + 2) * ((ww + 2) | 1) <= PATH_SMALL_CELLS;
-    const PathKind kind = path_kind(B, small);
+    const PathKind kind = path_kind(cx, B, small);
     PathScratch ps;
-    if (kind == PK_EARLY) path_scratch(ps, st, (size_t)B * SIMAPS_MAX_ROOM_CELLS * sizeof(float));
+    if (kind == PK_EARLY) path_scratch(cx, ps, st, (size_t)B * SIMAPS_MAX_ROOM_CELLS * sizeof(float));
     float *scratch = ps.p;
 #define SIMAPS_GRID_PATH_LAUNCH(C, E, O)                                                               \
     hipLaunchKernelGGL((grid_path_kernel<C, E, O>), dim3(B), dim3(PNT), 0, st, H, W, grids, sources, targets, wi0, wj0, \
-                       wh, ww, max_points, out_ij, out_count, scratch, g_fault_dev)
+                       wh, ww, max_points, out_ij, out_count, scratch, cx.fault_dev)
     if (kind == PK_OVL) {
         if (small) SIMAPS_GRID_PATH_LAUNCH(PATH_SMALL_CELLS, true, true);
         else SIMAPS_GRID_PATH_LAUNCH(SIMAPS_MAX_ROOM_CELLS, true, true);
@@ -4722,7 +4808,8 @@ int simaps_grid_path(int B, int H, int W, const uint8_t *grids, const int32_t *s
     return 0;
 }
 
-int simaps_sssp_grid(int B, int H, int W, const uint8_t *grids, const int32_t *sources, float *dists, int wi0, int wj0,
+static int sssp_grid_impl(simaps_ctx &cx, int B, int H, int W, const uint8_t *grids, const int32_t *sources,
+                          float *dists, int wi0, int wj0,
                      int wh, int ww, void *stream)
 {
     if (B < 0 || H <= 0 || W <= 0) return fail(SIMAPS_EINVAL, "bad batch / grid shape");
@@ -4732,30 +4819,31 @@ int simaps_sssp_grid(int B, int H, int W, const uint8_t *grids, const int32_t *s
         return fail(SIMAPS_EINVAL, "window outside the grid");
     if (H > 32767 || W > 32767) return fail(SIMAPS_EINVAL, "grid %dx%d too large", H, W);
     if (!window_fits_lds(wh, ww)) {  // any larger window: the global-memory sweeps (grid_large.h)
-        if (const int rc = pending_faults()) return rc;
+        if (const int rc = pending_faults(cx)) return rc;
         const hipStream_t st = (hipStream_t)stream;
         const long cells = (long)(wh + 2) * (ww + 2);
         PathScratch ps;
-        if (const int rc = large_scratch(ps, st, (size_t)B * cells * sizeof(float), "sssp_grid")) return rc;
+        if (const int rc = large_scratch(cx, ps, st, (size_t)B * cells * sizeof(float), "sssp_grid")) return rc;
         if (gl_tiled(wh, ww))
             hipLaunchKernelGGL(gl_tile_kernel, dim3(B), dim3(GT_NT), 0, st, H, W, grids, (long)H * W, sources, wi0, wj0, wh,
-                               ww, ps.p, cells, dists, g_fault_dev);
+                               ww, ps.p, cells, dists, cx.fault_dev);
         else
             hipLaunchKernelGGL(gl_sssp_kernel, dim3(B), dim3(GL_NT), 0, st, H, W, grids, (long)H * W, sources, wi0, wj0, wh,
-                               ww, ps.p, cells, dists, g_fault_dev);
+                               ww, ps.p, cells, dists, cx.fault_dev);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(SIMAPS_EHIP, "sssp_grid (large window) launch: %s", hipGetErrorString(e));
         return 0;
     }
-    if (const int rc = pending_faults()) return rc;
+    if (const int rc = pending_faults(cx)) return rc;
     hipLaunchKernelGGL(sssp_grid_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, H, W, grids, sources, dists, wi0,
-                       wj0, wh, ww, g_fault_dev);
+                       wj0, wh, ww, cx.fault_dev);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "sssp_grid launch: %s", hipGetErrorString(e));
     return 0;
 }
 
-int simaps_occupancy_scatter(const simaps_config *cfg, int N, const simaps_agent *agents, const float *points,
+static int occupancy_scatter_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                  const float *points,
                              const float *seg, int P, double obstacle_seg_value, uint8_t *occupancy, void *stream)
 {
     int rc = check_cfg(cfg);
@@ -4764,7 +4852,7 @@ int simaps_occupancy_scatter(const simaps_config *cfg, int N, const simaps_agent
     if (N == 0 || P == 0) return 0;
     if (!agents || !points || !seg || !occupancy) return fail(SIMAPS_EINVAL, "NULL buffer");
     if (N > 65535) return fail(SIMAPS_EUNSUPPORTED, "%d maps per launch (grid y <= 65535)", N);
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     hipLaunchKernelGGL(occupancy_scatter_kernel, dim3((P + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, cfg->H,
                        cfg->W, P, agents, points, seg, obstacle_seg_value, occupancy);
     const hipError_t e = hipGetLastError();
@@ -4772,7 +4860,8 @@ int simaps_occupancy_scatter(const simaps_config *cfg, int N, const simaps_agent
     return 0;
 }
 
-static int occupancy_map_launch(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int occupancy_map_launch(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                const simaps_env *envs,
                          const simaps_robot *robots, const uint8_t *occupancy, uint8_t *cspace, uint8_t *thin,
                          const int32_t *pixels, int Q, int32_t *snapped, void *stream)
 {
@@ -4782,34 +4871,38 @@ static int occupancy_map_launch(const simaps_config *cfg, int N, const simaps_ag
     if (N == 0) return 0;
     if (!agents || !envs || !robots || !occupancy) return fail(SIMAPS_EINVAL, "NULL buffer");
     if (N > 65535) return fail(SIMAPS_EUNSUPPORTED, "%d agents per launch (grid y <= 65535)", N);
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     const int chunks = snapped ? (Q + OCC_SNAP_PER_WG - 1) / OCC_SNAP_PER_WG : 1;
     if (chunks == 0) return 0;
     hipLaunchKernelGGL(occupancy_map_kernel, dim3(chunks, N), dim3(PNT), 0, (hipStream_t)stream, *cfg, geometry(), agents,
-                       envs, robots, occupancy, cspace, thin, pixels, Q, snapped, g_fault_dev);
+                       envs, robots, occupancy, cspace, thin, pixels, Q, snapped, cx.fault_dev);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "occupancy_map launch: %s", hipGetErrorString(e));
     return 0;
 }
 
-int simaps_build_cspace(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int build_cspace_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                             const simaps_env *envs,
                         const simaps_robot *robots, const uint8_t *occupancy, uint8_t *cspace, uint8_t *cspace_thin,
                         void *stream)
 {
     if (!cspace && !cspace_thin) return fail(SIMAPS_EINVAL, "neither cspace nor cspace_thin requested");
-    return occupancy_map_launch(cfg, N, agents, envs, robots, occupancy, cspace, cspace_thin, nullptr, 0, nullptr, stream);
+    return occupancy_map_launch(cx, cfg, N, agents, envs, robots, occupancy, cspace, cspace_thin, nullptr, 0, nullptr,
+                                stream);
 }
 
-int simaps_snap_sources(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int snap_sources_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                             const simaps_env *envs,
                         const simaps_robot *robots, const uint8_t *occupancy, const int32_t *pixels, int Q,
                         int32_t *out, void *stream)
 {
     if (Q > 0 && (!pixels || !out)) return fail(SIMAPS_EINVAL, "NULL buffer");
     if (Q == 0) return 0;
-    return occupancy_map_launch(cfg, N, agents, envs, robots, occupancy, nullptr, nullptr, pixels, Q, out, stream);
+    return occupancy_map_launch(cx, cfg, N, agents, envs, robots, occupancy, nullptr, nullptr, pixels, Q, out, stream);
 }
 
-int simaps_global_maps(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+static int global_maps_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                            const simaps_env *envs,
                        const simaps_robot *robots, const double *paths, const float *overhead, float *overhead_map,
                        float *robot_map, float *history_map, float *intention_map, void *stream)
 {
@@ -4818,13 +4911,306 @@ int simaps_global_maps(const simaps_config *cfg, int N, const simaps_agent *agen
     if (N < 0) return fail(SIMAPS_EINVAL, "N < 0");
     if (N == 0 || (!overhead_map && !robot_map && !history_map && !intention_map)) return 0;
     if (!agents || !envs || !robots || !paths || (overhead_map && !overhead)) return fail(SIMAPS_EINVAL, "NULL buffer");
-    if ((rc = pending_faults())) return rc;
+    if ((rc = pending_faults(cx))) return rc;
     hipLaunchKernelGGL(global_maps_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geometry(), agents, envs,
-                       robots, paths, overhead, overhead_map, robot_map, history_map, intention_map, g_fault_dev);
+                       robots, paths, overhead, overhead_map, robot_map, history_map, intention_map, cx.fault_dev);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "global_maps launch: %s", hipGetErrorString(e));
     return 0;
 }
+
+// ---- context management (include/simaps_ctx.h) ---------------------------------------------------
+
+int simaps_ctx_create(int device, simaps_ctx **out)
+{
+    if (!out) return fail(SIMAPS_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (device < -1) return fail(SIMAPS_EINVAL, "device %d: an ordinal >= 0, or -1 for the current device", device);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        (void)hipGetLastError();
+        return fail(SIMAPS_EHIP, "no usable GPU (hipGetDeviceCount)");
+    }
+    if (device >= count) return fail(SIMAPS_EINVAL, "device %d: this process sees %d device(s)", device, count);
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(SIMAPS_EHIP, "hipGetDevice failed");
+    simaps_ctx *cx = new (std::nothrow) simaps_ctx;
+    if (!cx) return fail(SIMAPS_EHIP, "out of host memory");
+    cx->device = device;
+    {
+        const DeviceGuard on(*cx);
+        if (!on.ok || !fault_word(*cx)) {
+            if (cx->fault_host) (void)hipHostFree((void *)cx->fault_host);
+            delete cx;
+            return fail(SIMAPS_EHIP, "could not allocate the host-mapped fault record on device %d", device);
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        g_ctx_live.push_back(cx);
+    }
+    *out = cx;
+    return 0;
+}
+
+int simaps_ctx_destroy(simaps_ctx *ctx)
+{
+    if (!ctx) return fail(SIMAPS_EINVAL, "ctx is NULL (the default context cannot be destroyed)");
+    {
+        std::lock_guard<std::mutex> lk(g_ctx_mu);
+        size_t k = 0;
+        while (k < g_ctx_live.size() && g_ctx_live[k] != ctx) k++;
+        if (k == g_ctx_live.size())
+            return fail(SIMAPS_EINVAL, "context handle %p is not a live context (never created, or already destroyed)",
+                        (void *)ctx);
+        g_ctx_live.erase(g_ctx_live.begin() + k);
+    }
+    int rc = 0;
+    {
+        // every launch through the context has completed before its record and pool go away
+        const DeviceGuard on(*ctx);
+        if (!on.ok || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(SIMAPS_EHIP, "could not synchronise device %d", ctx->device);
+        }
+        for (hipMemPool_t p : ctx->pool)
+            if (p) (void)hipMemPoolDestroy(p);
+        if (ctx->fault_host) (void)hipHostFree((void *)ctx->fault_host);
+    }
+    delete ctx;
+    return rc;
+}
+
+int simaps_ctx_device(const simaps_ctx *ctx)
+{
+    const simaps_ctx *cx = resolve_ctx(ctx);
+    return cx ? cx->device : SIMAPS_EINVAL;
+}
+
+int simaps_ctx_fault_info(simaps_ctx *ctx, int clear, int *kernel, int *unit)
+{
+    if (kernel) *kernel = -1;
+    if (unit) *unit = -1;
+    simaps_ctx *cx = resolve_ctx(ctx);
+    if (!cx) return SIMAPS_EINVAL;
+    if (!fault_word(*cx)) return fail(SIMAPS_EHIP, "could not allocate the host-mapped fault word");
+    unsigned where = 0;
+    const unsigned f = read_faults(*cx, clear != 0, &where);
+    if (where) {
+        if (kernel) *kernel = (int)(where >> 24);
+        if (unit) *unit = (int)(where & 0xFFFFFFu);
+    }
+    return (int)f;
+}
+
+int simaps_ctx_fault_status(simaps_ctx *ctx, int clear) { return simaps_ctx_fault_info(ctx, clear, nullptr, nullptr); }
+
+int simaps_ctx_path_mode(simaps_ctx *ctx, int mode)
+{
+    simaps_ctx *cx = resolve_ctx(ctx);
+    if (!cx) return SIMAPS_EINVAL;
+    if (mode < 0 || mode > 3) return fail(SIMAPS_EINVAL, "path mode %d not in 0..3", mode);
+    return cx->path_mode.exchange(mode);
+}
+
+// ---- the compute entry points: simaps_<name> on the default context, simaps_ctx_<name> on the given
+// one (on its device for the duration of the call)
+#define SIMAPS_ON_CTX(ctx, call)                                                                      \
+    do {                                                                                              \
+        simaps_ctx *cx_ = resolve_ctx(ctx);                                                           \
+        if (!cx_) return SIMAPS_EINVAL;                                                               \
+        const DeviceGuard on_(*cx_);                                                                  \
+        if (!on_.ok) return fail(SIMAPS_EHIP, "could not switch to the context's device %d", cx_->device); \
+        simaps_ctx &cx = *cx_;                                                                        \
+        return call;                                                                                  \
+    } while (0)
+
+int simaps_get_state(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                     const simaps_robot *robots, const double *paths, const uint8_t *occupancy, const float *overhead,
+                     float *state, int num_robots_per_env, const simaps_debug *dbg, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, num_robots_per_env, dbg,
+                          stream);
+}
+int simaps_ctx_get_state(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                         const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                         const uint8_t *occupancy, const float *overhead, float *state, int num_robots_per_env,
+                         const simaps_debug *dbg, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
+        num_robots_per_env, dbg, stream));
+}
+
+int simaps_get_state_mixed(const simaps_config *cfgs, const int32_t *num_robots_per_env, int n_cfgs, int N,
+                           const simaps_agent *agents, const int32_t *agent_cfg, const simaps_env *envs,
+                           const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                           const int64_t *map_off, const float *overhead, float *state, const int64_t *out_off,
+                           void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_mixed_impl(cx, cfgs, num_robots_per_env, n_cfgs, N, agents, agent_cfg, envs, robots, paths,
+                                occupancy, map_off, overhead, state, out_off, stream);
+}
+int simaps_ctx_get_state_mixed(simaps_ctx *ctx, const simaps_config *cfgs, const int32_t *num_robots_per_env,
+                               int n_cfgs, int N, const simaps_agent *agents, const int32_t *agent_cfg,
+                               const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                               const uint8_t *occupancy, const int64_t *map_off, const float *overhead, float *state,
+                               const int64_t *out_off, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, get_state_mixed_impl(cx, cfgs, num_robots_per_env, n_cfgs, N, agents, agent_cfg, envs, robots,
+        paths, occupancy, map_off, overhead, state, out_off, stream));
+}
+
+int simaps_sp_distance(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                       const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
+                       const double *targets, int Q, double *out, void *rec_cache, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return sp_distance_impl(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, Q, out, rec_cache, stream);
+}
+int simaps_ctx_sp_distance(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                           const simaps_env *envs, const simaps_robot *robots, const uint8_t *occupancy,
+                           const double *sources, const double *targets, int Q, double *out, void *rec_cache,
+                           void *stream)
+{
+    SIMAPS_ON_CTX(ctx, sp_distance_impl(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, Q, out,
+        rec_cache, stream));
+}
+
+int simaps_sp_lookup(const simaps_config *cfg, int N, const simaps_agent *agents, const void *rec_cache,
+                     const double *targets, int Q, double *out, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return sp_lookup_impl(cx, cfg, N, agents, rec_cache, targets, Q, out, stream);
+}
+int simaps_ctx_sp_lookup(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                         const void *rec_cache, const double *targets, int Q, double *out, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, sp_lookup_impl(cx, cfg, N, agents, rec_cache, targets, Q, out, stream));
+}
+
+int simaps_shortest_path(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                         const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
+                         const double *targets, int max_points, double *out_xy, int32_t *out_count, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return shortest_path_impl(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, max_points, out_xy,
+                              out_count, stream);
+}
+int simaps_ctx_shortest_path(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                             const simaps_env *envs, const simaps_robot *robots, const uint8_t *occupancy,
+                             const double *sources, const double *targets, int max_points, double *out_xy,
+                             int32_t *out_count, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, shortest_path_impl(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, max_points,
+        out_xy, out_count, stream));
+}
+
+int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, const simaps_agent *agents,
+                  const simaps_seg_ids *seg_ids, const double *cam_params, const float *depth, const int32_t *seg_raw,
+                  float *overhead, uint8_t *occupancy, uint64_t *keys, uint32_t *boxes, int epoch, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return ingest_impl(cx, cfg, cam, N, agents, seg_ids, cam_params, depth, seg_raw, overhead, occupancy, keys, boxes,
+                       epoch, stream);
+}
+int simaps_ctx_ingest(simaps_ctx *ctx, const simaps_config *cfg, const simaps_camera *cam, int N,
+                      const simaps_agent *agents, const simaps_seg_ids *seg_ids, const double *cam_params,
+                      const float *depth, const int32_t *seg_raw, float *overhead, uint8_t *occupancy, uint64_t *keys,
+                      uint32_t *boxes, int epoch, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, ingest_impl(cx, cfg, cam, N, agents, seg_ids, cam_params, depth, seg_raw, overhead, occupancy,
+        keys, boxes, epoch, stream));
+}
+
+int simaps_sssp_grid(int B, int H, int W, const uint8_t *grids, const int32_t *sources, float *dists, int wi0, int wj0,
+                     int wh, int ww, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return sssp_grid_impl(cx, B, H, W, grids, sources, dists, wi0, wj0, wh, ww, stream);
+}
+int simaps_ctx_sssp_grid(simaps_ctx *ctx, int B, int H, int W, const uint8_t *grids, const int32_t *sources,
+                         float *dists, int wi0, int wj0, int wh, int ww, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, sssp_grid_impl(cx, B, H, W, grids, sources, dists, wi0, wj0, wh, ww, stream));
+}
+
+int simaps_grid_path(int B, int H, int W, const uint8_t *grids, const int32_t *sources, const int32_t *targets,
+                     int wi0, int wj0, int wh, int ww, int max_points, int32_t *out_ij, int32_t *out_count,
+                     void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return grid_path_impl(cx, B, H, W, grids, sources, targets, wi0, wj0, wh, ww, max_points, out_ij, out_count,
+                          stream);
+}
+int simaps_ctx_grid_path(simaps_ctx *ctx, int B, int H, int W, const uint8_t *grids, const int32_t *sources,
+                         const int32_t *targets, int wi0, int wj0, int wh, int ww, int max_points, int32_t *out_ij,
+                         int32_t *out_count, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, grid_path_impl(cx, B, H, W, grids, sources, targets, wi0, wj0, wh, ww, max_points, out_ij,
+        out_count, stream));
+}
+
+int simaps_occupancy_scatter(const simaps_config *cfg, int N, const simaps_agent *agents, const float *points,
+                             const float *seg, int P, double obstacle_seg_value, uint8_t *occupancy, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return occupancy_scatter_impl(cx, cfg, N, agents, points, seg, P, obstacle_seg_value, occupancy, stream);
+}
+int simaps_ctx_occupancy_scatter(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                 const float *points, const float *seg, int P, double obstacle_seg_value,
+                                 uint8_t *occupancy, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, occupancy_scatter_impl(cx, cfg, N, agents, points, seg, P, obstacle_seg_value, occupancy,
+        stream));
+}
+
+int simaps_build_cspace(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                        const simaps_robot *robots, const uint8_t *occupancy, uint8_t *cspace, uint8_t *cspace_thin,
+                        void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return build_cspace_impl(cx, cfg, N, agents, envs, robots, occupancy, cspace, cspace_thin, stream);
+}
+int simaps_ctx_build_cspace(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                            const simaps_env *envs, const simaps_robot *robots, const uint8_t *occupancy,
+                            uint8_t *cspace, uint8_t *cspace_thin, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, build_cspace_impl(cx, cfg, N, agents, envs, robots, occupancy, cspace, cspace_thin, stream));
+}
+
+int simaps_snap_sources(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                        const simaps_robot *robots, const uint8_t *occupancy, const int32_t *pixels, int Q,
+                        int32_t *out, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return snap_sources_impl(cx, cfg, N, agents, envs, robots, occupancy, pixels, Q, out, stream);
+}
+int simaps_ctx_snap_sources(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                            const simaps_env *envs, const simaps_robot *robots, const uint8_t *occupancy,
+                            const int32_t *pixels, int Q, int32_t *out, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, snap_sources_impl(cx, cfg, N, agents, envs, robots, occupancy, pixels, Q, out, stream));
+}
+
+int simaps_global_maps(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                       const simaps_robot *robots, const double *paths, const float *overhead, float *overhead_map,
+                       float *robot_map, float *history_map, float *intention_map, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return global_maps_impl(cx, cfg, N, agents, envs, robots, paths, overhead, overhead_map, robot_map, history_map,
+                            intention_map, stream);
+}
+int simaps_ctx_global_maps(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                           const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                           const float *overhead, float *overhead_map, float *robot_map, float *history_map,
+                           float *intention_map, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, global_maps_impl(cx, cfg, N, agents, envs, robots, paths, overhead, overhead_map, robot_map,
+        history_map, intention_map, stream));
+}
+
+#undef SIMAPS_ON_CTX
 
 }  // extern "C"
 #endif  // SIMAPS_DEVICE_ONLY

@@ -17,7 +17,7 @@ __global__ void __launch_bounds__(NT) get_state_mixed_kernel(
     if ((unsigned)k >= (unsigned)mx.n) {
         // a configuration index past the table: reported, and the workgroup writes nothing (any
         // configuration's C channels at out_off[n] could run past the agent's own stack)
-        if (threadIdx.x == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR);
+        if (threadIdx.x == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GET_STATE_MIXED, blockIdx.x);
         return;
     }
     const simaps_config cfg = mx.cfg[k];

@@ -4,7 +4,8 @@ Submodules (imported lazily so that the pure-numpy ones -- constants, synthetic 
 without torch, e.g. from the python3.9 golden generator):
   constants  reference constants (envs.py)
   synthetic  seeded synthetic scenes
-  _lib       ctypes binding of libsimaps.so (the C-ABI in include/simaps.h)
+  _lib       ctypes binding of libsimaps.so (the C-ABI in include/simaps.h and include/simaps_ctx.h)
+  context    Context: a caller's own fault record, path mode and scratch pool (several GPUs / threads)
   batch      device-resident batched scene packing + the fused get_state launch, ingest, movement
              paths, reward lookups, raw-grid SSSP / paths
   vector_env drop-ins for VectorEnv.get_state (VectorEnvObservations) and GridGraph

@@ -1,4 +1,4 @@
-"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h).
+"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h and include/simaps_ctx.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -87,6 +87,19 @@ def _check_source_hash(L, path):
                                 'diagnostic builds)' % (path, built[:16], want[:16]))
 
 
+# include/simaps_ctx.h: the context functions, and the compute entry points that have a twin
+# simaps_ctx_<name> taking the context first
+CTX_MANAGEMENT = ('simaps_ctx_create', 'simaps_ctx_destroy', 'simaps_ctx_device', 'simaps_ctx_fault_status',
+                  'simaps_ctx_fault_info', 'simaps_ctx_path_mode')
+CTX_TWINS = ('get_state', 'get_state_mixed', 'sp_distance', 'sp_lookup', 'shortest_path', 'ingest', 'sssp_grid',
+             'grid_path', 'occupancy_scatter', 'build_cspace', 'snap_sources', 'global_maps')
+EXPORTED_CTX = CTX_MANAGEMENT + tuple('simaps_ctx_' + n for n in CTX_TWINS)
+
+# SIMAPS_K_* (include/simaps_ctx.h): kernel id of a fault record's `where` word -> kernel name
+K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
+           7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps'}
+
+
 def _load(path=LIB_PATH):
     """Bind the C ABI of the library at `path` (the product libsimaps.so by default; tests also load
     diagnostic builds of the same ABI through this)."""
@@ -141,6 +154,19 @@ def _load(path=LIB_PATH):
         L.simaps_snap_sources.restype = i32
         L.simaps_global_maps.argtypes = [ctypes.POINTER(Config), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.simaps_global_maps.restype = i32
+    if hasattr(L, 'simaps_ctx_create'):  # (include/simaps_ctx.h; absent only in an older revision's A/B build)
+        L.simaps_ctx_create.argtypes = [i32, ctypes.POINTER(vp)]
+        L.simaps_ctx_destroy.argtypes = [vp]
+        L.simaps_ctx_device.argtypes = [vp]
+        L.simaps_ctx_fault_status.argtypes = [vp, i32]
+        L.simaps_ctx_fault_info.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.simaps_ctx_path_mode.argtypes = [vp, i32]
+        for name in CTX_MANAGEMENT:
+            getattr(L, name).restype = i32
+        for name in CTX_TWINS:  # the context first, then the old entry point's argument list
+            twin = getattr(L, 'simaps_ctx_' + name)
+            twin.argtypes = [vp] + list(getattr(L, 'simaps_' + name).argtypes)
+            twin.restype = i32
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):
@@ -202,6 +228,23 @@ def check_faults(L=None):
         raise DeviceFault('device fault bits 0x%x (%s): the outputs of a completed launch are invalid' % (
             f, ' '.join(n for b, n in ((FAULT_TIMEOUT, 'barrier-timeout'), (FAULT_ROUNDS, 'sssp-round-cap'),
                                        (FAULT_DESCRIPTOR, 'descriptor-clamped')) if f & b)))
+
+
+def call(context, name, *args, L=None):
+    """The entry point simaps_<name> on the default context (context None), or its twin
+    simaps_ctx_<name> through `context` (a simaps.context.Context); returns the return code."""
+    L = L or lib
+    if context is None:
+        return getattr(L, 'simaps_' + name)(*args)
+    return getattr(L, 'simaps_ctx_' + name)(context.handle, *args)
+
+
+def check_context_faults(context=None, L=None):
+    """check_faults() for the default context, context.check_faults() for a created one."""
+    if context is None:
+        check_faults(L)
+    else:
+        context.check_faults()
 
 
 def stream_handle(stream=None):

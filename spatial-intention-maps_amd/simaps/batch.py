@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from . import constants as K
+from . import context as _context
 
 
 def make_config(flags, room_width, room_length, layout='hwc', rotate_rounding='fma'):
@@ -224,7 +225,7 @@ class StateBatch(_ArrayUpload):
     what a conv policy consumes) or 'hwc' (the reference's (96, 96, C) memory order).  as_hwc() gives
     the reference's index order as a zero-copy view either way."""
 
-    def __init__(self, scenes, agents=None, device='cuda', layout='chw'):
+    def __init__(self, scenes, agents=None, device='cuda', layout='chw', context=None):
         if not scenes:
             raise ValueError('a StateBatch needs at least one scene')
         s0 = scenes[0]
@@ -237,6 +238,7 @@ class StateBatch(_ArrayUpload):
         self.scenes, self.agents, self.device = scenes, list(agents), resolve_device(device)
         if self.device.type != 'cuda':
             raise ValueError('StateBatch renders on a GPU device (got %s); there is no CPU path' % self.device)
+        self.context = _context.for_device(context, self.device)  # None: the process-wide default context
         self.flags = s0['flags']
         self.H, self.W = s0['H'], s0['W']
         self.cfg = make_config(self.flags, s0['room_width'], s0['room_length'], layout,
@@ -376,10 +378,9 @@ class StateBatch(_ArrayUpload):
         s, cur = launch_stream(self.device, stream)
         if rec is not None:
             self._rec_wait(s)
-        _lib.check(_lib.lib.simaps_get_state(
-            self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d),
-            _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead), _lib.ptr(out),
-            self.num_robots if self.flags['use_intention_channels'] else 0,
+        _lib.check(_lib.call(self.context, 'get_state', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
+            _lib.ptr(out), self.num_robots if self.flags['use_intention_channels'] else 0,
             None if dbg is None else dbg, _lib.stream_handle(s)))
         hold(s, cur, out, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, self.overhead, rec,
              *(debug.values() if debug else ()))
@@ -407,9 +408,9 @@ class StateBatch(_ArrayUpload):
         s, cur = launch_stream(self.device, stream)
         if _rec is not None:
             self._rec_wait(s)
-        _lib.check(_lib.lib.simaps_sp_distance(
-            self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.occupancy),
-            _lib.ptr(src), _lib.ptr(tgt), Q, _lib.ptr(out), _lib.ptr(_rec), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'sp_distance', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.occupancy), _lib.ptr(src), _lib.ptr(tgt), Q, _lib.ptr(out),
+            _lib.ptr(_rec), _lib.stream_handle(s)))
         hold(s, cur, src, tgt, out, agents_d, self.envs_d, self.robots_d, self.occupancy, _rec)
         if _rec is not None:
             self._rec_record(s)
@@ -494,8 +495,8 @@ class StateBatch(_ArrayUpload):
                         else (self.agents_d, self.N)
                     o = dst if dst is not None else torch.empty((m, Q), dtype=torch.float64, device=self.device)
                     self._rec_wait(s)
-                    _lib.check(_lib.lib.simaps_sp_lookup(self.cfg, m, _lib.ptr(agents_d), _lib.ptr(rec), _lib.ptr(th),
-                                                         Q, _lib.ptr(o), _lib.stream_handle(s)))
+                    _lib.check(_lib.call(self.context, 'sp_lookup', self.cfg, m, _lib.ptr(agents_d), _lib.ptr(rec),
+                        _lib.ptr(th), Q, _lib.ptr(o), _lib.stream_handle(s)))
                     hold(s, cur, agents_d, th, o)
                     self._rec_record(s)
                 if sub is not None:
@@ -526,9 +527,8 @@ class StateBatch(_ArrayUpload):
         if out is self.occupancy:
             self._map_ver[slice(None) if slots is None else np.asarray(list(slots), dtype=np.int64)] += 1
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_occupancy_scatter(self.cfg, n, _lib.ptr(agents_d), _lib.ptr(pts), _lib.ptr(sg),
-                                                     pts.shape[1], float(obstacle_seg_value), _lib.ptr(out),
-                                                     _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'occupancy_scatter', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(pts),
+            _lib.ptr(sg), pts.shape[1], float(obstacle_seg_value), _lib.ptr(out), _lib.stream_handle(s)))
         hold(s, cur, agents_d, pts, sg, out)
 
     def build_cspace(self, slots=None, cspace=True, thin=True, stream=None):
@@ -541,8 +541,8 @@ class StateBatch(_ArrayUpload):
         if n == 0 or (cs is None and th is None):
             return cs, th
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_build_cspace(self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d),
-                                                _lib.ptr(self.occupancy), _lib.ptr(cs), _lib.ptr(th), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'build_cspace', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.occupancy), _lib.ptr(cs), _lib.ptr(th), _lib.stream_handle(s)))
         hold(s, cur, agents_d, self.occupancy, cs, th)
         return cs, th
 
@@ -559,8 +559,8 @@ class StateBatch(_ArrayUpload):
         if n == 0 or Q == 0:
             return out
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_snap_sources(self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d),
-                                                _lib.ptr(self.occupancy), _lib.ptr(px), Q, _lib.ptr(out), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'snap_sources', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.occupancy), _lib.ptr(px), Q, _lib.ptr(out), _lib.stream_handle(s)))
         hold(s, cur, agents_d, self.occupancy, px, out)
         return out
 
@@ -582,10 +582,10 @@ class StateBatch(_ArrayUpload):
         if n == 0:
             return out
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_global_maps(self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d),
-                                               _lib.ptr(self.paths_d), _lib.ptr(self.overhead), _lib.ptr(out['overhead']),
-                                               _lib.ptr(out.get('robot')), _lib.ptr(out.get('history')),
-                                               _lib.ptr(out.get('intention')), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'global_maps', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.overhead), _lib.ptr(out['overhead']),
+            _lib.ptr(out.get('robot')), _lib.ptr(out.get('history')), _lib.ptr(out.get('intention')),
+            _lib.stream_handle(s)))
         hold(s, cur, agents_d, self.envs_d, self.robots_d, self.paths_d, self.overhead, *out.values())
         return out
 
@@ -600,7 +600,7 @@ class StateBatch(_ArrayUpload):
                       dtype=np.int32).reshape(n, 1, 2)
         src = self.snap_pixels(px, slots=slots)[:, 0, :]
         i0, j0, h, w = self.cfg.room_i0, self.cfg.room_j0, self.cfg.room_h, self.cfg.room_w
-        img = sssp_grid(cs, src, window=(i0, j0, h, w))
+        img = sssp_grid(cs, src, window=(i0, j0, h, w), context=self.context)
         return img / np.float32(K.LOCAL_MAP_PIXELS_PER_METER)
 
     def shortest_paths(self, sources, targets, slots=None, max_points=64, stream=None):
@@ -616,7 +616,7 @@ class StateBatch(_ArrayUpload):
         if s != cur:
             cur.wait_stream(s)
         xy, cnt = xy.cpu().numpy(), cnt.cpu().numpy()
-        _lib.check_faults()
+        _lib.check_context_faults(self.context)
         if (cnt < 0).any():
             raise RuntimeError('a path has %d waypoints > max_points=%d' % (-cnt.min(), max_points))
         return _point_lists(xy, cnt, 0)
@@ -635,9 +635,9 @@ class StateBatch(_ArrayUpload):
         if n == 0:
             return xy, cnt
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_shortest_path(
-            self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.occupancy),
-            _lib.ptr(src), _lib.ptr(tgt), max_points, _lib.ptr(xy), _lib.ptr(cnt), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'shortest_path', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.occupancy), _lib.ptr(src), _lib.ptr(tgt), max_points, _lib.ptr(xy),
+            _lib.ptr(cnt), _lib.stream_handle(s)))
         hold(s, cur, src, tgt, xy, cnt, agents_d, self.envs_d, self.robots_d, self.occupancy)
         return xy, cnt
 
@@ -737,10 +737,10 @@ class StateBatch(_ArrayUpload):
                     self._keys.zero_()
                 self._epoch = 1
             epoch = self._epoch
-        _lib.check(_lib.lib.simaps_ingest(
-            self.cfg, prep['cam'], prep['n'], _lib.ptr(prep['agents']), _lib.ptr(prep['ids']), _lib.ptr(prep['params']),
-            _lib.ptr(prep['depth']), _lib.ptr(prep['seg']), _lib.ptr(self.overhead), _lib.ptr(self.occupancy),
-            _lib.ptr(self._keys), _lib.ptr(self._boxes), epoch, _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'ingest', self.cfg, prep['cam'], prep['n'], _lib.ptr(prep['agents']),
+            _lib.ptr(prep['ids']), _lib.ptr(prep['params']), _lib.ptr(prep['depth']), _lib.ptr(prep['seg']),
+            _lib.ptr(self.overhead), _lib.ptr(self.occupancy), _lib.ptr(self._keys), _lib.ptr(self._boxes), epoch,
+            _lib.stream_handle(s)))
         if not capturing:
             self._ingest_stream = s
         hold(s, cur, prep['ids'], prep['params'], prep['depth'], prep['seg'], prep['agents'], self.overhead,
@@ -762,7 +762,7 @@ def _point_lists(pts, cnt, *extra):
     return out
 
 
-def sssp_grid(grids, sources, window=None, stream=None):
+def sssp_grid(grids, sources, window=None, stream=None, context=None):
     """Batched GridGraph(grid).shortest_path_image(source) on device.
 
     grids: uint8 tensor [B, H, W] (device), sources: int32 [B, 2].  window = (i0, j0, h, w) that
@@ -771,22 +771,24 @@ def sssp_grid(grids, sources, window=None, stream=None):
     B, H, W = grids.shape
     if window is None:
         window = (0, 0, H, W)
+    _context.for_device(context, grids.device)
     out = torch.empty((B, H, W), dtype=torch.float32, device=grids.device)
     src = sources.to(device=grids.device, dtype=torch.int32).contiguous()
     g = grids.contiguous()
     s, cur = launch_stream(grids.device, stream)
-    _lib.check(_lib.lib.simaps_sssp_grid(B, H, W, _lib.ptr(g), _lib.ptr(src), _lib.ptr(out),
-                                         *[int(x) for x in window], _lib.stream_handle(s)))
+    _lib.check(_lib.call(context, 'sssp_grid', B, H, W, _lib.ptr(g), _lib.ptr(src), _lib.ptr(out),
+        *[int(x) for x in window], _lib.stream_handle(s)))
     hold(s, cur, g, src, out)
     return out
 
 
-def launch_grid_paths(grids, sources, targets, window=None, max_points=256, stream=None):
+def launch_grid_paths(grids, sources, targets, window=None, max_points=256, stream=None, context=None):
     """The device half of grid_paths(): one call, results left on the device as (ij [B, max_points, 2]
     int32, count [B] int32; count = -needed if max_points is too small)."""
     B, H, W = grids.shape
     if window is None:
         window = (0, 0, H, W)
+    _context.for_device(context, grids.device)
     src = torch.as_tensor(sources).to(device=grids.device, dtype=torch.int32).contiguous()
     tgt = torch.as_tensor(targets).to(device=grids.device, dtype=torch.int32).contiguous()
     if tuple(src.shape) != (B, 2) or tuple(tgt.shape) != (B, 2):
@@ -797,13 +799,13 @@ def launch_grid_paths(grids, sources, targets, window=None, max_points=256, stre
         return ij, cnt
     g = grids.contiguous()
     s, cur = launch_stream(grids.device, stream)
-    _lib.check(_lib.lib.simaps_grid_path(B, H, W, _lib.ptr(g), _lib.ptr(src), _lib.ptr(tgt), *[int(x) for x in window],
-                                         max_points, _lib.ptr(ij), _lib.ptr(cnt), _lib.stream_handle(s)))
+    _lib.check(_lib.call(context, 'grid_path', B, H, W, _lib.ptr(g), _lib.ptr(src), _lib.ptr(tgt),
+        *[int(x) for x in window], max_points, _lib.ptr(ij), _lib.ptr(cnt), _lib.stream_handle(s)))
     hold(s, cur, g, src, tgt, ij, cnt)
     return ij, cnt
 
 
-def grid_paths(grids, sources, targets, window=None, max_points=256, stream=None, grow=False):
+def grid_paths(grids, sources, targets, window=None, max_points=256, stream=None, grow=False, context=None):
     """Batched GridGraph(grid).shortest_path(source, target) (pyx:121-154) on device.
 
     grids: uint8 tensor [B, H, W] (device), sources / targets: int [B, 2] cells.  Returns B lists of
@@ -813,15 +815,15 @@ def grid_paths(grids, sources, targets, window=None, max_points=256, stream=None
     B = grids.shape[0]
     if B == 0:
         return []
-    ij, cnt = launch_grid_paths(grids, sources, targets, window, max_points, stream)
+    ij, cnt = launch_grid_paths(grids, sources, targets, window, max_points, stream, context)
     s, cur = launch_stream(grids.device, stream)
     if s != cur:
         cur.wait_stream(s)
     ij, cnt = ij.cpu().numpy(), cnt.cpu().numpy()
-    _lib.check_faults()
+    _lib.check_context_faults(context)
     if (cnt < 0).any():
         if grow:
-            return grid_paths(grids, sources, targets, window, int(-cnt.min()), stream, grow=False)
+            return grid_paths(grids, sources, targets, window, int(-cnt.min()), stream, grow=False, context=context)
         raise RuntimeError('a path has %d waypoints > max_points=%d' % (-cnt.min(), max_points))
     return _point_lists(ij, cnt)
 
@@ -881,7 +883,7 @@ class MixedStateBatch(_ArrayUpload):
     agent's (C, 96, 96) (layout 'chw') or (96, 96, C) ('hwc') view of it, C that of its own
     configuration.  The results equal one StateBatch.render per configuration, bit for bit."""
 
-    def __init__(self, scenes, device='cuda', layout='chw'):
+    def __init__(self, scenes, device='cuda', layout='chw', context=None):
         if not scenes:
             raise ValueError('a MixedStateBatch needs at least one scene')
         if layout not in ('chw', 'hwc'):
@@ -889,6 +891,7 @@ class MixedStateBatch(_ArrayUpload):
         self.device = resolve_device(device)
         if self.device.type != 'cuda':
             raise ValueError('MixedStateBatch renders on a GPU device (got %s); there is no CPU path' % self.device)
+        self.context = _context.for_device(context, self.device)
         self.layout = layout
         self.plan = plan_mixed(scenes, layout)
         self.scenes, self.agents, self.N = scenes, self.plan['agents'], len(self.plan['agents'])
@@ -925,11 +928,11 @@ class MixedStateBatch(_ArrayUpload):
                 and out.device == self.device):
             raise ValueError('out must be a contiguous float32 tensor of %d elements on %s' % (self.plan['out_numel'], self.device))
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.lib.simaps_get_state_mixed(
-            self._cfgs, self._nrs.ctypes.data, len(self.plan['cfgs']), self.N, _lib.ptr(self.agents_d),
-            _lib.ptr(self.agent_cfg_d), _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.paths_d),
-            _lib.ptr(self.occupancy), _lib.ptr(self.map_off_d), _lib.ptr(self.overhead), _lib.ptr(out),
-            _lib.ptr(self.out_off_d), _lib.stream_handle(s)))
+        _lib.check(_lib.call(self.context, 'get_state_mixed', self._cfgs, self._nrs.ctypes.data,
+            len(self.plan['cfgs']), self.N, _lib.ptr(self.agents_d), _lib.ptr(self.agent_cfg_d),
+            _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy),
+            _lib.ptr(self.map_off_d), _lib.ptr(self.overhead), _lib.ptr(out), _lib.ptr(self.out_off_d),
+            _lib.stream_handle(s)))
         hold(s, cur, out, self.agents_d, self.agent_cfg_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy,
              self.map_off_d, self.overhead, self.out_off_d)
         return out

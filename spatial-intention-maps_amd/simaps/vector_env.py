@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import batch as _batch
+from . import context as _context
 
 
 def robot_groups(scene):
@@ -40,15 +41,17 @@ class VectorEnvObservations:
     (C, 96, 96) planes (what a conv policy consumes, policies.py:44-45) -- states returned by
     get_state() are always the reference's (96, 96, C) index order (views for 'chw')."""
 
-    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0):
+    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0, context=None):
         """reuse_outputs=R > 0: all-robots get_state() renders into a ring of R preallocated output
         batches and returns a structure of views built once per ring slot (no per-call allocation
         or per-robot view creation: ~0.2 ms of host time per 256 stacks).  The states of a call are
         then overwritten R calls later -- copy what must live longer (the reference returns fresh
         arrays; the default R = 0 keeps that).  With numpy=True the ring slots also hold a pinned
         host copy: one asynchronous device->host copy per call into page-locked memory, returned as
-        NumPy views (a fresh pageable copy per call otherwise)."""
-        self.batch = _batch.StateBatch(scenes, device=device, layout=layout)
+        NumPy views (a fresh pageable copy per call otherwise).
+        context: a simaps.context.Context that every launch and fault check of this object goes
+        through (None: the process-wide default context)."""
+        self.batch = _batch.StateBatch(scenes, device=device, layout=layout, context=context)
         self._ring = [None] * int(reuse_outputs)
         self._ring_k = 0
         self._hring = [None] * int(reuse_outputs)  # (device batch, pinned host batch, NumPy views)
@@ -126,7 +129,7 @@ class VectorEnvObservations:
             with torch.cuda.stream(s):
                 host.copy_(buf, non_blocking=True)
             s.synchronize()
-            _lib.check_faults()  # the copy completed: a faulting launch raises here
+            _lib.check_context_faults(self.batch.context)  # the copy completed: a faulting launch raises here
             return views
         if all_robots or awaiting is None:  # every robot: the batch's own agent list, structure precomputed
             out = self.batch.as_hwc(self.batch.render(stream=stream))
@@ -134,7 +137,7 @@ class VectorEnvObservations:
                 if stream is not None:
                     torch.cuda.current_stream(self.batch.device).wait_stream(stream)
                 out = out.cpu().numpy()
-                _lib.check_faults()
+                _lib.check_context_faults(self.batch.context)
             rows = out if numpy else out.unbind(0)
             return [[[rows[k] for k in g] for g in env] for env in self._all_slots]
         want = []
@@ -147,7 +150,7 @@ class VectorEnvObservations:
             if stream is not None:
                 torch.cuda.current_stream(self.batch.device).wait_stream(stream)
             out = out.cpu().numpy()
-            _lib.check_faults()  # the copy synchronised: a faulting launch raises here
+            _lib.check_context_faults(self.batch.context)  # the copy synchronised: a faulting launch raises here
         pos = {k: n for n, k in enumerate(want)}
         rows = out if numpy else out.unbind(0)  # one C++ call for all views (per-item indexing: ~10 us each)
         res = []
@@ -170,7 +173,7 @@ class VectorEnvObservations:
         slots = [self.slot[(e, a)] for e, a, _ in todo]
         pos = [self.batch.scenes[e]['robots'][a]['position'][:2] for e, a, _ in todo]
         maps = figures.device_global_maps(self.batch, slots, pos)
-        _lib.check_faults()
+        _lib.check_context_faults(self.batch.context)
         for (e, a, st), gm in zip(todo, maps):
             s = self.batch.scenes[e]
             rid = s['robots'][a].get('id', '%d_%d' % (e, a))
@@ -202,7 +205,7 @@ class VectorEnvObservations:
             if stream is not None:
                 torch.cuda.current_stream(self.batch.device).wait_stream(stream)
             d = d.cpu().numpy()
-            _lib.check_faults()
+            _lib.check_context_faults(self.batch.context)
         else:
             d = np.zeros((n, 0))
         return [[[float(x) for x in d[self.slot[(e, a)], :len(positions[e][a])]] for a in range(len(positions[e]))]
@@ -247,11 +250,12 @@ class GridGraph:
     beyond the LDS-resident limits of include/simaps.h (every reference call site passes a room
     cspace, which fits), the C ABI runs the global-memory kernels instead (`large` is then True)."""
 
-    def __init__(self, grid, device='cuda'):
+    def __init__(self, grid, device='cuda', context=None):
         g = torch.as_tensor(np.ascontiguousarray(grid) if isinstance(grid, np.ndarray) else grid)
         if g.dim() != 2:
             raise ValueError('grid must be 2-D')
         self.device = _batch.resolve_device(device)
+        self.context = _context.for_device(context, self.device)  # None: the default context
         self.grid = g.to(device=self.device, dtype=torch.uint8).contiguous()
         self.shape = tuple(self.grid.shape)
         free = torch.nonzero(self.grid)
@@ -275,7 +279,8 @@ class GridGraph:
         todo = [s for s in dict.fromkeys(srcs) if s not in self._cache]
         if todo:
             grids = self.grid.unsqueeze(0).expand(len(todo), *self.shape).contiguous()
-            imgs = _batch.sssp_grid(grids, torch.tensor(todo, dtype=torch.int32), window=self.window, stream=stream)
+            imgs = _batch.sssp_grid(grids, torch.tensor(todo, dtype=torch.int32), window=self.window, stream=stream,
+                                    context=self.context)
             if stream is not None:  # cached images are read on the current stream by later calls
                 torch.cuda.current_stream(self.device).wait_stream(stream)
             for k, s in enumerate(todo):
@@ -286,7 +291,7 @@ class GridGraph:
     def shortest_path_image(self, source):
         """(H, W) float32 NumPy image of distances from `source` (pyx:165-167)."""
         img = self.shortest_path_images([source])[0].cpu().numpy()
-        _lib.check_faults()
+        _lib.check_context_faults(self.context)
         return img
 
     def shortest_path(self, source, target):
@@ -301,7 +306,8 @@ class GridGraph:
             return []
         grids = self.grid.unsqueeze(0).expand(len(pairs), *self.shape).contiguous()
         return _batch.grid_paths(grids, [p[0] for p in pairs], [p[1] for p in pairs], window=self.window,
-                                 max_points=max(256, self.shape[0] + self.shape[1]), stream=stream, grow=True)
+                                 max_points=max(256, self.shape[0] + self.shape[1]), stream=stream, grow=True,
+                                 context=self.context)
 
     def shortest_path_distance(self, source, target):
         """dists[target] from `source` as a Python float (pyx:156-163); -1 if unreachable."""
@@ -335,7 +341,7 @@ class OccupancyMap:
     save_figure: the free-space map is marked on the device by the same scatter kernel, the figure is a
     headless matplotlib Figure (no window, no plt.pause)."""
 
-    def __init__(self, robot, room_length, room_width, show_map=False, device='cuda'):
+    def __init__(self, robot, room_length, room_width, show_map=False, device='cuda', context=None):
         from . import constants as K
         self.robot = robot
         self.room_length, self.room_width = room_length, room_width
@@ -349,7 +355,7 @@ class OccupancyMap:
                  'flags': dict(K.DEFAULT_FLAGS), 'robot_config': [{typ: 1}], 'H': H, 'W': W,
                  'receptacle_position': None, 'robots': [rob],
                  'occupancy': np.zeros((1, H, W), np.uint8), 'overhead': np.zeros((1, H, W), np.float32)}
-        self._b = _batch.StateBatch([scene], device=device)
+        self._b = _batch.StateBatch([scene], device=device, context=context)
         self._cspace = self._thin = self._closest = None
         self.grid_graph = None
         if self.show_map:  # envs.py:2434-2443
@@ -388,7 +394,7 @@ class OccupancyMap:
             ii, jj = torch.meshgrid(torch.arange(H, dtype=torch.int32), torch.arange(W, dtype=torch.int32), indexing='ij')
             px = torch.stack([ii, jj], -1).reshape(1, H * W, 2)
             out = self._b.snap_pixels(px).cpu().numpy()
-            _lib.check_faults()
+            _lib.check_context_faults(self._b.context)
             self._closest = out[0].T.reshape(2, H, W).copy()
         return self._closest
 
@@ -438,7 +444,7 @@ class OccupancyMap:
     def _derive(self):
         cs, th = self._b.build_cspace()
         self._cspace, self._thin, self._closest = cs[0], th[0], None
-        self.grid_graph = GridGraph(self._cspace, device=self._b.device)
+        self.grid_graph = GridGraph(self._cspace, device=self._b.device, context=self._b.context)
 
     def _need_update(self):
         if self._cspace is None:
@@ -447,7 +453,7 @@ class OccupancyMap:
     def _closest_valid_cspace_indices(self, i, j):
         self._need_update()
         out = self._b.snap_pixels(torch.tensor([[[int(i), int(j)]]], dtype=torch.int32)).cpu().numpy()
-        _lib.check_faults()
+        _lib.check_context_faults(self._b.context)
         return out[0, 0]
 
     def _pixel(self, position):
@@ -469,7 +475,7 @@ class OccupancyMap:
         d = self._b.shortest_path_distances(np.array([[float(source_position[0]), float(source_position[1])]]),
                                             np.array([[[float(target_position[0]), float(target_position[1])]]]))
         d = float(d.cpu().numpy()[0, 0])
-        _lib.check_faults()
+        _lib.check_context_faults(self._b.context)
         return d
 
     def shortest_path_image(self, position):
