@@ -46,7 +46,7 @@
 
 #include "geom.h"
 #include "mixed.h"
-#include "simaps_ctx.h"  // (includes simaps.h)
+#include "simaps_action.h"  // (includes simaps_ctx.h, which includes simaps.h)
 
 using namespace simaps;
 
@@ -4099,6 +4099,7 @@ __global__ void __launch_bounds__(INGEST_RES_WG) ingest_resolve_kernel(
 #include "grid_large.h"
 #include "occupancy_map.h"
 #include "global_maps.h"
+#include "action.h"
 #endif
 
 }  // namespace
@@ -4230,7 +4231,7 @@ const char *kernel_name(unsigned id)
 {
     static const char *const names[SIMAPS_K_COUNT + 1] = {
         "?", "get_state", "get_state_mixed", "sp_distance", "path", "sssp_grid", "grid_path", "gl_sssp", "gl_tile",
-        "gl_path", "occupancy_map", "global_maps"};
+        "gl_path", "occupancy_map", "global_maps", "action"};
     return id <= SIMAPS_K_COUNT ? names[id] : "?";
 }
 
@@ -4660,18 +4661,13 @@ static int sp_distance_impl(simaps_ctx &cx, const simaps_config *cfg, int N, con
     return 0;
 }
 
-static int shortest_path_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
-                              const simaps_env *envs,
-                         const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
-                         const double *targets, int max_points, double *out_xy, int32_t *out_count, void *stream)
+// the path launch itself, after the argument and fault checks (simaps_store_new_action launches it
+// between its own two kernels, under its own entry check)
+static int shortest_path_launch(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                const simaps_env *envs, const simaps_robot *robots, const uint8_t *occupancy,
+                                const double *sources, const double *targets, int max_points, double *out_xy,
+                                int32_t *out_count, void *stream)
 {
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if (N < 0 || max_points < 2) return fail(SIMAPS_EINVAL, "N < 0 or max_points < 2");
-    if (N == 0) return 0;
-    if (!agents || !envs || !robots || !occupancy || !sources || !targets || !out_xy || !out_count)
-        return fail(SIMAPS_EINVAL, "NULL buffer");
-    if ((rc = pending_faults(cx))) return rc;
     const Geometry &geo = geometry();
     const bool small = (cfg->room_h + 2) * ((cfg->room_w + 2) | 1) <= PATH_SMALL_CELLS;
     const hipStream_t st = (hipStream_t)stream;
@@ -4695,6 +4691,63 @@ static int shortest_path_impl(simaps_ctx &cx, const simaps_config *cfg, int N, c
 #undef SIMAPS_PATH_LAUNCH
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "shortest_path launch: %s", hipGetErrorString(e));
+    return 0;
+}
+
+static int shortest_path_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                              const simaps_env *envs,
+                         const simaps_robot *robots, const uint8_t *occupancy, const double *sources,
+                         const double *targets, int max_points, double *out_xy, int32_t *out_count, void *stream)
+{
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (N < 0 || max_points < 2) return fail(SIMAPS_EINVAL, "N < 0 or max_points < 2");
+    if (N == 0) return 0;
+    if (!agents || !envs || !robots || !occupancy || !sources || !targets || !out_xy || !out_count)
+        return fail(SIMAPS_EINVAL, "NULL buffer");
+    if ((rc = pending_faults(cx))) return rc;
+    return shortest_path_launch(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, max_points, out_xy,
+                                out_count, stream);
+}
+
+// simaps_store_new_action (include/simaps_action.h): decode, path, finish on the caller's stream.  One
+// entry check for the three launches: a fault the decode kernel posts for a bad action must fail
+// the context's NEXT call, not the path launch of this one.
+static int store_new_action_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                 const simaps_env *envs, simaps_robot *robots, double *paths, const uint8_t *occupancy,
+                                 const float *q, const int64_t *q_off, const int32_t *actions_in, int flags,
+                                 int max_points, int32_t *out_action, double *out_source, double *out_target,
+                                 double *out_xy, double *out_heading, int32_t *out_count, void *stream)
+{
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (N < 0 || max_points < 2) return fail(SIMAPS_EINVAL, "N < 0 or max_points < 2");
+    if (flags & ~(SIMAPS_ACTION_SHORTEST_PATH | SIMAPS_ACTION_WRITE_BACK)) return fail(SIMAPS_EINVAL, "unknown flag bits 0x%x", flags);
+    if ((q == nullptr) != (q_off == nullptr)) return fail(SIMAPS_EINVAL, "q and q_off must both be given or both be NULL");
+    if (!q && !actions_in) return fail(SIMAPS_EINVAL, "neither q nor actions_in");
+    if (!out_action || !out_source || !out_target || !out_xy || !out_heading || !out_count)
+        return fail(SIMAPS_EINVAL, "NULL output");
+    const bool spm = flags & SIMAPS_ACTION_SHORTEST_PATH, wb = flags & SIMAPS_ACTION_WRITE_BACK;
+    if (!agents || !envs || !robots || (spm && !occupancy) || (wb && !paths)) return fail(SIMAPS_EINVAL, "NULL buffer");
+    if (N == 0) return 0;
+    if ((rc = pending_faults(cx))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(action_decode_kernel, dim3(N), dim3(ACT_NT), 0, st, agents, envs, robots, q, q_off, actions_in,
+                       flags, max_points, out_action, out_source, out_target, out_xy, out_count, cx.fault_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SIMAPS_EHIP, "store_new_action decode launch: %s", hipGetErrorString(e));
+    if (spm && (rc = shortest_path_launch(cx, cfg, N, agents, envs, robots, occupancy, out_source, out_target,
+                                          max_points, out_xy, out_count, stream)))
+        return rc;
+    const Geometry &geo = geometry();
+    ActionOffsets off;
+    for (int t = 0; t < 4; t++)  // END_EFFECTOR_LOCATION + CUBE_WIDTH / 2 (envs.py:889)
+        off.ee[t] = (geo.backpack_offset + geo.base_length[t]) + geo.cube_width / 2;
+    hipLaunchKernelGGL(action_finish_kernel, dim3((N + ACT_FIN_NT - 1) / ACT_FIN_NT), dim3(ACT_FIN_NT), 0, st, N, agents,
+                       envs, robots, paths, actions_in, q != nullptr, flags, max_points, off, out_target, out_xy,
+                       out_heading, out_count);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(SIMAPS_EHIP, "store_new_action finish launch: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -5104,6 +5157,35 @@ int simaps_ctx_shortest_path(simaps_ctx *ctx, const simaps_config *cfg, int N, c
 {
     SIMAPS_ON_CTX(ctx, shortest_path_impl(cx, cfg, N, agents, envs, robots, occupancy, sources, targets, max_points,
         out_xy, out_count, stream));
+}
+
+int simaps_action_abi_version(void) { return SIMAPS_ACTION_ABI_VERSION; }
+
+int simaps_num_output_channels(int type)
+{
+    if (type < 0 || type > 3) return fail(SIMAPS_EINVAL, "robot class %d", type);
+    return action_channels(type);
+}
+
+int simaps_store_new_action(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                            simaps_robot *robots, double *paths, const uint8_t *occupancy, const float *q,
+                            const int64_t *q_off, const int32_t *actions_in, int flags, int max_points,
+                            int32_t *out_action, double *out_source, double *out_target, double *out_xy,
+                            double *out_heading, int32_t *out_count, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return store_new_action_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in, flags,
+                                 max_points, out_action, out_source, out_target, out_xy, out_heading, out_count, stream);
+}
+int simaps_ctx_store_new_action(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                const simaps_env *envs, simaps_robot *robots, double *paths,
+                                const uint8_t *occupancy, const float *q, const int64_t *q_off,
+                                const int32_t *actions_in, int flags, int max_points, int32_t *out_action,
+                                double *out_source, double *out_target, double *out_xy, double *out_heading,
+                                int32_t *out_count, void *stream)
+{
+    SIMAPS_ON_CTX(ctx, store_new_action_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in,
+        flags, max_points, out_action, out_source, out_target, out_xy, out_heading, out_count, stream));
 }
 
 int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, const simaps_agent *agents,

@@ -1,4 +1,5 @@
-"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h and include/simaps_ctx.h).
+"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h and
+include/simaps_action.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -29,6 +30,7 @@ ROBOT_DTYPE = np.dtype([('x', '<f8'), ('y', '<f8'), ('heading', '<f8'), ('target
 ENV_DTYPE = np.dtype([('receptacle_x', '<f8'), ('receptacle_y', '<f8'), ('has_receptacle', '<i4'),
                       ('robot_off', '<i4'), ('num_robots', '<i4'), ('reserved', '<i4')], align=True)
 ABI_VERSION = 8  # include/simaps.h SIMAPS_ABI_VERSION
+ACTION_ABI_VERSION = 1  # include/simaps_action.h SIMAPS_ACTION_ABI_VERSION
 MAX_MIXED = 8  # SIMAPS_MAX_MIXED
 AGENT_DTYPE = np.dtype([('env', '<i4'), ('robot', '<i4'), ('map_slot', '<i4')], align=True)
 assert ROBOT_DTYPE.itemsize == 72 and ENV_DTYPE.itemsize == 32 and AGENT_DTYPE.itemsize == 12
@@ -96,8 +98,13 @@ CTX_TWINS = ('get_state', 'get_state_mixed', 'sp_distance', 'sp_lookup', 'shorte
 EXPORTED_CTX = CTX_MANAGEMENT + tuple('simaps_ctx_' + n for n in CTX_TWINS)
 
 # SIMAPS_K_* (include/simaps_ctx.h): kernel id of a fault record's `where` word -> kernel name
+# include/simaps_action.h: the step back from the policy (its compute entry point has a context twin too)
+EXPORTED_ACTION = ('simaps_action_abi_version', 'simaps_num_output_channels', 'simaps_store_new_action',
+                   'simaps_ctx_store_new_action')
+ACTION_SHORTEST_PATH, ACTION_WRITE_BACK = 1, 2  # SIMAPS_ACTION_* flag bits
+
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
-           7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps'}
+           7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action'}
 
 
 def _load(path=LIB_PATH):
@@ -167,6 +174,19 @@ def _load(path=LIB_PATH):
             twin = getattr(L, 'simaps_ctx_' + name)
             twin.argtypes = [vp] + list(getattr(L, 'simaps_' + name).argtypes)
             twin.restype = i32
+    if hasattr(L, 'simaps_store_new_action'):  # (include/simaps_action.h; absent only in an older revision's A/B build)
+        L.simaps_action_abi_version.restype = i32
+        L.simaps_num_output_channels.argtypes = [i32]
+        L.simaps_num_output_channels.restype = i32
+        L.simaps_store_new_action.argtypes = [ctypes.POINTER(Config), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                              vp, vp, vp, vp, vp, vp, vp]
+        L.simaps_store_new_action.restype = i32
+        L.simaps_ctx_store_new_action.argtypes = [vp] + list(L.simaps_store_new_action.argtypes)
+        L.simaps_ctx_store_new_action.restype = i32
+        va = L.simaps_action_abi_version()
+        if va != ACTION_ABI_VERSION:
+            raise ImportError('libsimaps action ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, va, ACTION_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

@@ -5,8 +5,8 @@ One function computes it for both sides: the Makefile runs this file to pass the
 library built from other sources -- a stale binary left over from before a kernel edit.  The
 reference rebuilds its extension from its own source the same way (shortest_paths/setup.py:1-6).
 
-Hashed: every `.hip` / `.h` / `.inc` file of spatial-intention-maps_amd/csrc, include/simaps.h and
-include/simaps_ctx.h, in sorted relative-path order, each as `path NUL content NUL`.  Comments count: any edit of a
+Hashed: every `.hip` / `.h` / `.inc` file of spatial-intention-maps_amd/csrc, include/simaps.h,
+include/simaps_ctx.h and include/simaps_action.h, in sorted relative-path order, each as `path NUL content NUL`.  Comments count: any edit of a
 kernel source makes the library stale until it is rebuilt.
 """
 import hashlib
@@ -24,6 +24,7 @@ def source_files(pkg_root=PKG_ROOT, repo_root=None):
              if os.path.splitext(f)[1] in ('.hip', '.h', '.inc')]
     files.append(('include/simaps.h', os.path.join(repo_root, 'include', 'simaps.h')))
     files.append(('include/simaps_ctx.h', os.path.join(repo_root, 'include', 'simaps_ctx.h')))
+    files.append(('include/simaps_action.h', os.path.join(repo_root, 'include', 'simaps_action.h')))
     return sorted(files)
 
 

@@ -215,7 +215,25 @@ class _ArrayUpload:
         self._stage_ev[k] = ev
         self.robots_d = dev[:R * _lib.ROBOT_DTYPE.itemsize]
         self.paths_d = dev[self._rob_bytes:]
+        self._paths_reserved = True  # simaps_pack_robots' layout: MAX_PATH points per path (store_new_actions write_back)
         self.pose_host = pose.copy()  # the poses packed above (the caller may update its array in place)
+
+
+class ActionResult:
+    """What StateBatch.store_new_actions leaves on the device, per agent of the call: action [n] int32
+    (the flat index; the reference's tuple is np.unravel_index(action, (K, 96, 96))), source [n, 2] and
+    target [n, 2] fp64 (current position, target_end_effector_position[:2]), xy [n, max_points, 2]
+    (waypoint_positions[:, :2]), heading [n, max_points] (waypoint_headings), count [n] int32
+    (waypoints; -needed if max_points was too small; 0 for an agent whose action was out of range,
+    which the context's next call also reports)."""
+
+    def __init__(self, action, source, target, xy, heading, count, max_points):
+        self.action, self.source, self.target = action, source, target
+        self.xy, self.heading, self.count, self.max_points = xy, heading, count, max_points
+
+    def to_host(self):
+        """One synchronising download: dict of NumPy arrays of the same names."""
+        return {k: getattr(self, k).cpu().numpy() for k in ('action', 'source', 'target', 'xy', 'heading', 'count')}
 
 
 class StateBatch(_ArrayUpload):
@@ -273,6 +291,7 @@ class StateBatch(_ArrayUpload):
         """Upload a new per-step scene descriptor (poses, controller state, paths)."""
         robots, envs, ag, paths = pack_descriptors(scenes, self.agents)
         self.scenes = scenes
+        self._paths_reserved = False  # packed back to back: no room to write a new path in place
         if hasattr(self, '_rec_ver'):
             self._rec_ver[:] = -1  # new scenes may move a receptacle: no cached array stays valid
         # per map slot: its env's receptacle (x, y) (receptacle_distances' SSSP source)
@@ -640,6 +659,79 @@ class StateBatch(_ArrayUpload):
             _lib.ptr(cnt), _lib.stream_handle(s)))
         hold(s, cur, src, tgt, xy, cnt, agents_d, self.envs_d, self.robots_d, self.occupancy)
         return xy, cnt
+
+    def store_new_actions(self, q=None, q_off=None, actions=None, slots=None, use_shortest_path_movement=True,
+                          max_points=64, write_back=False, stream=None):
+        """Robot.store_new_action (envs.py:857-903) behind DQNPolicy.step's arg-max (policies.py:61-65)
+        for map slots `slots` (all agents if None), in one stream-ordered device call
+        (simaps_store_new_action, include/simaps_action.h); no synchronisation, everything stays on
+        the device.  The policy outputs come as
+          q a float32 device tensor and q_off [n] int64 float offsets of each agent's [K, 96, 96] block;
+          q an [n, K, 96, 96] tensor, q_off None: agent i's block is q[i] (one K for all n);
+          q a list of (tensor [n_g, K_g, 96, 96], positions) pairs, one per robot group: row i of a
+            group belongs to the call's agent positions[i]; concatenated here (one copy), q_off built;
+          q None: every agent's action is given.
+        actions: [n] int32 (array or device tensor), >= 0 the action index to use (the host's
+        epsilon-greedy draw, policy_output.select_actions), -1 the arg-max; None: all arg-max.
+        write_back=True also stores target, idle = 0 and the new intention / history paths into the
+        device descriptors the next render() reads; needs the layout of set_descriptor_arrays().
+        -> ActionResult of device tensors."""
+        agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
+        if q is None and actions is None:
+            raise ValueError('store_new_actions needs q, actions or both')
+        if write_back and not getattr(self, '_paths_reserved', False):
+            raise ValueError('write_back needs the descriptor layout of set_descriptor_arrays() (room for a new path '
+                             'per robot); set_descriptors() packs the paths back to back')
+        if max_points < 2:
+            raise ValueError('max_points must be at least 2')
+        plane = K.LOCAL_MAP_PIXEL_WIDTH * K.LOCAL_MAP_PIXEL_WIDTH
+        if isinstance(q, (list, tuple)):
+            off = np.full(n, -1, dtype=np.int64)
+            base, parts = 0, []
+            for t, positions in q:
+                if t is None or not len(positions):
+                    continue
+                if t.dim() != 4 or t.shape[0] != len(positions) or tuple(t.shape[2:]) != (K.LOCAL_MAP_PIXEL_WIDTH,) * 2:
+                    raise ValueError('each group output must be [len(positions), K, 96, 96]')
+                off[np.asarray(positions, dtype=np.int64)] = base + np.arange(len(positions), dtype=np.int64) * t.shape[1] * plane
+                base += t.numel()
+                parts.append(t.to(device=self.device, dtype=torch.float32).reshape(-1))
+            if actions is None and (off < 0).any():
+                raise ValueError('agent %d has neither a policy output nor an action' % int(np.argmax(off < 0)))
+            off[off < 0] = 0  # (agents with a given action: their block is not read)
+            q, q_off = (torch.cat(parts) if parts else None), off
+            if q is None:
+                q_off = None
+        elif q is not None and q_off is None:
+            if q.dim() != 4 or q.shape[0] != n or tuple(q.shape[2:]) != (K.LOCAL_MAP_PIXEL_WIDTH,) * 2:
+                raise ValueError('q must be [%d, K, 96, 96] when q_off is not given' % n)
+            q_off = np.arange(n, dtype=np.int64) * q.shape[1] * plane
+        if q is not None:
+            if not (q.is_cuda and q.device == self.device and q.dtype == torch.float32):
+                raise ValueError('q must be a float32 tensor on %s' % self.device)
+            q = q.contiguous()
+            q_off = torch.as_tensor(q_off, dtype=torch.int64).to(self.device).contiguous()
+            if tuple(q_off.shape) != (n,):
+                raise ValueError('q_off must be [%d]' % n)
+        act = None
+        if actions is not None:
+            act = torch.as_tensor(actions, dtype=torch.int32).to(self.device).contiguous()
+            if tuple(act.shape) != (n,):
+                raise ValueError('actions must be [%d]' % n)
+        i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=self.device)  # noqa: E731
+        f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=self.device)  # noqa: E731
+        res = ActionResult(i32(n), f64(n, 2), f64(n, 2), f64(n, max_points, 2), f64(n, max_points), i32(n), max_points)
+        if n == 0:
+            return res
+        flags = (_lib.ACTION_SHORTEST_PATH if use_shortest_path_movement else 0) | (_lib.ACTION_WRITE_BACK if write_back else 0)
+        s, cur = launch_stream(self.device, stream)
+        _lib.check(_lib.call(self.context, 'store_new_action', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(q), _lib.ptr(q_off),
+            _lib.ptr(act), flags, max_points, _lib.ptr(res.action), _lib.ptr(res.source), _lib.ptr(res.target),
+            _lib.ptr(res.xy), _lib.ptr(res.heading), _lib.ptr(res.count), _lib.stream_handle(s)))
+        hold(s, cur, q, q_off, act, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, res.action,
+             res.source, res.target, res.xy, res.heading, res.count)
+        return res
 
     def ingest(self, depth, seg_raw, camera='forward', slots=None, seg_ids=None, stream=None):
         """Robot.update_map minus the simulator (envs.py:925, 2056-2066) for map slots `slots` (all

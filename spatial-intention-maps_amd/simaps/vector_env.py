@@ -230,6 +230,68 @@ class VectorEnvObservations:
         return paths
 
 
+    # -- the step back from the policy ---------------------------------------------------------------
+    def store_new_action(self, action=None, outputs=None, use_shortest_path_movement=True, max_points=64,
+                         write_back=False, stream=None):
+        """VectorEnv.store_new_action(action) (envs.py:224-228 -> Robot.store_new_action, 857-903) for
+        every env of the batch in one device call.  action: [env][group][robot] -> action index or
+        None, the structure DQNPolicy.step returns per env; outputs (optional): per env, per group
+        (robot indices within the group, [n, K, 96, 96] device batch or None) -- the networks' outputs
+        in the structure policy_input.group_batches gives their inputs.  A robot with an index acts on
+        it; a robot with None (or -1) in `action`, or with no `action` at all, takes the arg-max of its
+        row of `outputs` if it has one, and does not act otherwise.
+        -> [env][group][robot] -> None, or a dict with the robot's new `action` ((channel, row, col)),
+        `target_end_effector_position` ((x, y, 0)), `waypoint_positions` ([(x, y, 0), ...]) and
+        `waypoint_headings`, as the reference's attributes of those names read afterwards.
+        write_back=True: the device descriptors take the new targets and paths, so the next
+        get_state() sees them without a host re-pack (needs update_arrays() descriptors)."""
+        order, given, rows = [], [], {}
+        for e in range(self.num_envs):
+            for g, members in enumerate(self.groups[e]):
+                idx, bt = outputs[e][g] if outputs is not None else ([], None)
+                have = {j: i for i, j in enumerate(idx)} if bt is not None else {}
+                for j, a in enumerate(members):
+                    act = action[e][g][j] if action is not None else None
+                    act = -1 if act is None else int(act)
+                    if act < 0 and j not in have:
+                        continue
+                    if act < 0:
+                        rows.setdefault((e, g), ([], []))
+                        rows[(e, g)][0].append(have[j])
+                        rows[(e, g)][1].append(len(order))
+                    order.append((e, g, j, a))
+                    given.append(act)
+        res = [[[None] * len(m) for m in self.groups[e]] for e in range(self.num_envs)]
+        if not order:
+            return res
+        q = None
+        if rows:
+            q = []
+            for (e, g), (src_rows, positions) in rows.items():
+                bt = outputs[e][g][1]
+                pick = bt if src_rows == list(range(bt.shape[0])) else bt[torch.as_tensor(src_rows, device=bt.device)]
+                q.append((pick, positions))
+        slots = [self.slot[(e, a)] for e, _, _, a in order]
+        r = self.batch.store_new_actions(q=q, actions=np.asarray(given, dtype=np.int32), slots=slots,
+                                         use_shortest_path_movement=use_shortest_path_movement, max_points=max_points,
+                                         write_back=write_back, stream=stream)
+        if stream is not None:
+            torch.cuda.current_stream(self.batch.device).wait_stream(stream)
+        h = r.to_host()
+        _lib.check_context_faults(self.batch.context)
+        if (h['count'] < 0).any():
+            raise RuntimeError('a path has %d waypoints > max_points=%d' % (-h['count'].min(), max_points))
+        W = _batch.K.LOCAL_MAP_PIXEL_WIDTH
+        for n, (e, g, j, _) in enumerate(order):
+            c, a = int(h['count'][n]), int(h['action'][n])
+            res[e][g][j] = {
+                'action': (a // (W * W), a % (W * W) // W, a % W),
+                'target_end_effector_position': (float(h['target'][n, 0]), float(h['target'][n, 1]), 0),
+                'waypoint_positions': [(float(x), float(y), 0) for x, y in h['xy'][n, :c]],
+                'waypoint_headings': [float(v) for v in h['heading'][n, :c]]}
+        return res
+
+
 MAX_WINDOW_CELLS, MAX_WINDOW_W = 9024, 120  # SIMAPS_MAX_ROOM_CELLS / SIMAPS_MAX_ROOM_W (include/simaps.h)
 
 

@@ -7,6 +7,9 @@
   env_step       (--env-step) the device time of one reference VectorEnv.step: paths, ingest, get_state
   mixed          (--mixed) one launch over envs of the BASELINE configurations together
                  (simaps_get_state_mixed) vs one launch per configuration back to back
+  store_new_action (--action) the step back from the policy (simaps_store_new_action): device time
+                 of the call and of its decode kernel, and the wall time per step against the same
+                 result composed from torch arg-max + numpy + shortest_paths + set_descriptor_arrays
   gridgraph_large (--gridgraph-large) GridGraph on a 500 x 500 grid (beyond the LDS window: the
                  global-memory kernels of csrc/grid_large.h): images and paths, 1 and 64 per call
 
@@ -207,6 +210,147 @@ def bench_env_step(args):
           flush=True)
 
 
+def _host_store_new_action(b, q, slots, arr, rob_idx, ee_offset, P):
+    """The new call's result composed from what the library offered before it: torch arg-max +
+    .tolist(), numpy geometry, the movement-path launch + download, numpy post-processing (vectorised
+    over the robots), set_descriptor_arrays.  Robot.store_new_action, envs.py:857-903."""
+    n = len(slots)
+    a = np.asarray(q.view(n, -1).argmax(1).tolist())
+    rem = a % 9216
+    row, col = rem // 96, rem % 96
+    dx, dy = ((col + 0.5) - 48.0) / 96.0, (48.0 - (row + 0.5)) / 96.0
+    pos, heading = arr['pose'][rob_idx, :2], arr['pose'][rob_idx, 2]
+    dist = np.sqrt(dx * dx + dy * dy)
+    theta = heading + np.arctan2(-dx, dy)
+    tgt = pos + dist[:, None] * np.stack([np.cos(theta), np.sin(theta)], 1)
+    xy, cnt = b.launch_shortest_paths(pos, tgt, slots=slots, max_points=P)
+    xy, cnt = xy.cpu().numpy(), cnt.cpu().numpy()
+    rh = lambda h: (h + np.pi) % (2 * np.pi) - np.pi  # noqa: E731
+    d = xy[:, 1:] - xy[:, :-1]
+    hd = np.concatenate([heading[:, None], rh(np.arctan2(d[..., 1], d[..., 0]))], 1)
+    k = np.arange(n)
+    last = cnt - 1
+    e = xy[k, last] - xy[k, last - 1]
+    sd = np.sqrt(e[:, 0] ** 2 + e[:, 1] ** 2) - ee_offset
+    hl = hd[k, last]
+    xy[k, last] = xy[k, last - 1] + sd[:, None] * np.stack([np.cos(hl), np.sin(hl)], 1)
+    fix = np.nonzero((cnt > 2) & (sd < 0))[0]
+    if len(fix):
+        lf = last[fix]
+        xy[fix, lf - 1] = xy[fix, lf]
+        e = xy[fix, lf - 1] - xy[fix, lf - 2]
+        hd[fix, lf - 1] = rh(np.arctan2(e[:, 1], e[:, 0]))
+    arr['target'][rob_idx] = tgt
+    arr['idle'][rob_idx] = False
+    arr['waypoints'][rob_idx] = xy
+    arr['wp_count'][rob_idx] = cnt
+    arr['wp_index'][rob_idx] = 1
+    b.set_descriptor_arrays(**arr)
+    return a, tgt, xy, hd, cnt
+
+
+def bench_action(args):
+    """The step back from the policy (include/simaps_action.h) for `awaiting` robots of 64 envs of
+    lifting_4-small_divider, Q maps resident on the device as the networks leave them:
+    (a) device time by HIP events after warm-up: the whole call (decode, path, finish; write-back on),
+        and the decode kernel: the call without the path launch, with the Q maps read minus with every
+        action given (the same two launches, the decode workgroups then skip their Q block) -- the
+        difference is the Q read, reported with its bytes per second;
+    (b) wall time per step, synchronised, results downloaded to the host in both routes: the new call
+        (store_new_actions(write_back=True) + one download) against _host_store_new_action; the two
+        alternate step by step in this process; medians."""
+    from simaps import _lib, constants as K
+    scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
+    A = len(scenes[0]['robots'])
+    P = _lib.MAX_PATH
+    lines = []
+    for n in args.awaiting:
+        b = batch.StateBatch(scenes)
+        slots = list(range(b.N)) if n == b.N else [e * A + (e % A) for e in range(args.envs)][:n]
+        assert len(slots) == n
+        rob_idx = np.asarray(slots)  # (every agent in order: slot k is robot k)
+        arr = batch.descriptor_arrays(scenes)
+        w = np.zeros((b.n_robots, P, 2))
+        w[:, :arr['waypoints'].shape[1]] = arr['waypoints']
+        arr['waypoints'] = w
+        b.set_descriptor_arrays(**arr)
+        q = torch.randn(n, 2, 96, 96, generator=torch.Generator().manual_seed(1)).cuda()
+        given = torch.as_tensor(q.view(n, -1).argmax(1), dtype=torch.int32)
+        ee = K.ROBOT_GEOM['lifting_robot']['END_EFFECTOR_LOCATION'] + K.CUBE_WIDTH / 2  # envs.py:889
+        s = torch.cuda.current_stream()
+        qf, q_off = q.view(-1), torch.arange(n, dtype=torch.int64, device='cuda') * (2 * 9216)
+        parts = {'call': lambda: b.store_new_actions(q=qf, q_off=q_off, slots=slots, max_points=P, write_back=True),
+                 'paths_alone': lambda: b.launch_shortest_paths(src_d, tgt_d, slots=slots, max_points=P),
+                 'decode_finish': lambda: b.store_new_actions(q=qf, q_off=q_off, slots=slots, max_points=P,
+                                                              use_shortest_path_movement=False),
+                 'finish_given': lambda: b.store_new_actions(q=qf, q_off=q_off, actions=given, slots=slots, max_points=P,
+                                                             use_shortest_path_movement=False)}
+        big = torch.randn(8192, 8192, device='cuda')
+        r0 = parts['call']()
+        src_d, tgt_d = r0.source.clone(), r0.target.clone()
+        res = {}
+        reps = max(args.steps, 50)
+        for name, f in parts.items():
+            for _ in range(5):
+                f()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            # a few ms of other work first: the calls below queue up behind it and then run back to
+            # back, so the events see the device time and not the host's ~30 us per Python call
+            torch.mm(big, big)
+            e0.record(s)
+            for _ in range(reps):
+                f()
+            e1.record(s)
+            torch.cuda.synchronize()
+            res[name + '_us'] = e0.elapsed_time(e1) / reps * 1e3
+        nbytes = n * 2 * 9216 * 4
+        dec = res['decode_finish_us'] - res['finish_given_us']
+        lines.append(dict({'row': 'store_new_action_device', 'config': args.config, 'awaiting_robots': n,
+                           'q_bytes': nbytes, 'decode_us': dec, 'decode_GBps': nbytes / max(dec, 1e-3) / 1e3,
+                           'decode_share_of_call': dec / res['call_us'],
+                           'note': 'HIP events around %d calls queued behind a blocking kernel (device-bound) after warm-up; '
+                                   'decode_finish / finish_given: the call without the path launch, Q maps read / every '
+                                   'action given (the decode workgroups skip the read); decode_us is their difference'
+                                   % reps}, **res))
+        print(json.dumps(lines[-1]), flush=True)
+
+        def new_route():
+            h = b.store_new_actions(q=q, slots=slots, max_points=P, write_back=True).to_host()
+            torch.cuda.synchronize()
+            return h
+
+        def new_route_device_only():
+            b.store_new_actions(q=q, slots=slots, max_points=P, write_back=True)
+            torch.cuda.synchronize()
+
+        def old_route():
+            r = _host_store_new_action(b, q, slots, arr, rob_idx, ee, P)
+            torch.cuda.synchronize()
+            return r
+        for _ in range(5):
+            new_route(), old_route(), new_route_device_only()
+        h, o = new_route(), old_route()
+        assert np.array_equal(h['action'], o[0]) and np.array_equal(h['count'], o[4])  # the same result
+        tn, to, td = [], [], []
+        for _ in range(max(args.steps, 200)):
+            for f, acc in ((new_route, tn), (old_route, to), (new_route_device_only, td)):
+                t0 = time.perf_counter()
+                f()
+                acc.append(time.perf_counter() - t0)
+        mn, mo, md = (float(np.median(t)) * 1e3 for t in (tn, to, td))
+        lines.append({'row': 'store_new_action_step', 'config': args.config, 'awaiting_robots': n,
+                      'new_ms': mn, 'composed_ms': mo, 'speedup': mo / mn, 'new_without_download_ms': md,
+                      'note': 'wall time per step, synchronised, medians of %d alternating steps: new = '
+                              'store_new_actions(write_back) + download of the results; composed = torch arg-max + '
+                              '.tolist(), numpy geometry, launch_shortest_paths + download, vectorised numpy '
+                              'post-processing, set_descriptor_arrays' % len(tn)})
+        print(json.dumps(lines[-1]), flush=True)
+    out = os.path.join(ROOT, 'profiles', 'action_bench.jsonl')
+    with open(out, 'w') as f:
+        f.write(''.join(json.dumps(x) + '\n' for x in lines))
+
+
 def bench_remap(args):
     """The periodic re-map of one moving robot (RobotController.step -> update_map every 200
     simulation steps, envs.py:1401-1403): a single-frame simaps_ingest, end to end (host prep +
@@ -382,6 +526,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if '--gridgraph-large' in sys.argv:
         bench_gridgraph_large()
+        sys.exit(0)
+    if '--action' in sys.argv:
+        bench_action(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, awaiting=(64, 256)))
         sys.exit(0)
     if '--env-step' in sys.argv:
         bench_env_step(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, all=False))
