@@ -2,7 +2,8 @@
 // GS_MIXED 0 / 1: with GS_MIXED the workgroup's configuration, its map slot's offset and its stack's
 // offset come from the launch's tables (simaps_get_state_mixed) instead of the launch-wide arguments.
 // (A textual include rather than a template: get_state_kernel's source, and so its code, stay
-// exactly those of the single-configuration kernel.)
+// exactly those of the single-configuration kernel.)  With SIMAPS_STATE16 (simaps_state16.inc) state
+// is the 16-bit stack and RenderCtx converts at the store; nothing else differs.
 #if defined(SIMAPS_VGPR_CAP) && !GS_MIXED  // (timing-only A/B build: the LDS hidden from the occupancy estimate)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #else
@@ -56,6 +57,8 @@
     if (tid == 0) STAMP_NB(0);
 #if GS_MIXED
     float *out = state + (size_t)out_off[n];
+#elif defined(SIMAPS_STATE16)
+    uint16_t *out = state + (size_t)n * LW * LW * C;
 #else
     float *out = state + (size_t)n * LW * LW * C;
 #endif

@@ -47,6 +47,8 @@
 #include "geom.h"
 #include "mixed.h"
 #include "simaps_action.h"  // (includes simaps_ctx.h, which includes simaps.h)
+#include "simaps_state16.h"
+#include "state16.h"
 
 using namespace simaps;
 
@@ -1878,8 +1880,39 @@ __device__ __forceinline__ float tile_sample(const float *tile, int gi, int gj, 
 struct RenderCtx {
     const simaps_config &cfg;
     Shared &sh;
+#ifdef SIMAPS_STATE16  // (simaps_state16.inc: the stack's elements are 16-bit, converted at the store)
+    uint16_t *out;
+#else
     float *out;
+#endif
     int C, n;
+#ifdef SIMAPS_STATE16
+    // IEEE round-to-nearest-even float32 -> bf16 (SIMAPS_STATE16 1) / fp16 (2) bits: the compiler's
+    // fptrunc (v_cvt_pk_bf16_f32 / v_cvt_f16_f32 on gfx950), what tensor.to() gives
+    static __device__ __forceinline__ unsigned cvt16(float v)
+    {
+#if SIMAPS_STATE16 == 1
+        return __builtin_bit_cast(unsigned short, static_cast<__bf16>(v));
+#else
+        return __builtin_bit_cast(unsigned short, static_cast<_Float16>(v));
+#endif
+    }
+    // chw: a wave's 64 consecutive pixels are one 2-byte store per lane = one whole 128-byte line
+    __device__ __forceinline__ void put(int ch, int p, float v) const
+    {
+        unsigned idx = cfg.layout_chw ? ch * LW * LW + p : p * C + ch;
+        asm volatile("" : "+v"(idx));
+        *reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(out) + idx * 2u) = (uint16_t)cvt16(v);
+    }
+    // chw only: 4 consecutive pixels p .. p + 3 (p % 4 == 0) of channel ch, one 8-byte store
+    __device__ __forceinline__ void put4(int ch, int p, float4 v) const
+    {
+        unsigned idx = ch * LW * LW + p;
+        asm volatile("" : "+v"(idx));
+        *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(out) + idx * 2u) =
+            uint2{cvt16(v.x) | (cvt16(v.y) << 16), cvt16(v.z) | (cvt16(v.w) << 16)};
+    }
+#else
     __device__ __forceinline__ void put(int ch, int p, float v) const
     {
         unsigned idx = cfg.layout_chw ? ch * LW * LW + p : p * C + ch;  // < 96 * 96 * C: 32-bit
@@ -1894,6 +1927,7 @@ struct RenderCtx {
         asm volatile("" : "+v"(idx));
         *reinterpret_cast<float4 *>(reinterpret_cast<char *>(out) + idx * 4u) = v;
     }
+#endif
 };
 
 // A robot's stamp geometry (Mapper._create_global_robot_map, envs.py:2251-2276): the scipy rotate of
@@ -4545,7 +4579,7 @@ int simaps_robot_mask(int type, int with_cube, float *out)
 static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
                           const simaps_env *envs,
                      const simaps_robot *robots, const double *paths, const uint8_t *occupancy, const float *overhead,
-                     float *state, int num_robots_per_env, const simaps_debug *dbg, void *stream)
+                     void *state, int state_dtype, int num_robots_per_env, const simaps_debug *dbg, void *stream)
 {
     int rc = check_cfg(cfg);
     const Geometry &geo = geometry();
@@ -4563,15 +4597,23 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     simaps_debug d;
     memset(&d, 0, sizeof(d));
     if (dbg) d = *dbg;
+    if (state_dtype != SIMAPS_STATE_F32) {  // simaps_get_state_as: the 16-bit instantiations (simaps_state16.inc)
+        (state_dtype == SIMAPS_STATE_BF16 ? simaps_state16::launch_get_state_bf16 : simaps_state16::launch_get_state_f16)(
+            *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, C, d, cx.fault_dev,
+            (hipStream_t)stream);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_as launch: %s", hipGetErrorString(e));
+        return 0;
+    }
 #ifdef SIMAPS_VGPR_CAP
     static const hipError_t lds_ok =
         hipFuncSetAttribute((const void *)get_state_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (lds_ok != hipSuccess) return fail(SIMAPS_EHIP, "dynamic LDS of the VGPR-cap build");
     hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), LDS_BYTES, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, state, C, d, cx.fault_dev);
+                       robots, paths, occupancy, overhead, (float *)state, C, d, cx.fault_dev);
 #else
     hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, state, C, d, cx.fault_dev);
+                       robots, paths, occupancy, overhead, (float *)state, C, d, cx.fault_dev);
 #endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
@@ -5082,8 +5124,8 @@ int simaps_get_state(const simaps_config *cfg, int N, const simaps_agent *agents
                      float *state, int num_robots_per_env, const simaps_debug *dbg, void *stream)
 {
     simaps_ctx &cx = g_default_ctx;
-    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, num_robots_per_env, dbg,
-                          stream);
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, SIMAPS_STATE_F32,
+                          num_robots_per_env, dbg, stream);
 }
 int simaps_ctx_get_state(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
                          const simaps_env *envs, const simaps_robot *robots, const double *paths,
@@ -5091,7 +5133,40 @@ int simaps_ctx_get_state(simaps_ctx *ctx, const simaps_config *cfg, int N, const
                          const simaps_debug *dbg, void *stream)
 {
     SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
-        num_robots_per_env, dbg, stream));
+        SIMAPS_STATE_F32, num_robots_per_env, dbg, stream));
+}
+
+// ---- simaps_state16.h
+int simaps_state16_abi_version(void) { return SIMAPS_STATE16_ABI_VERSION; }
+
+// what simaps_get_state_as checks on top of simaps_get_state (N <= 0 is get_state_impl's to answer)
+static int check_state_as(int N, const void *state, int state_dtype)
+{
+    if (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16)
+        return fail(SIMAPS_EINVAL, "unknown state_dtype %d (SIMAPS_STATE_F32, _BF16 or _F16)", state_dtype);
+    if (N > 0 && !state) return fail(SIMAPS_EINVAL, "state is NULL");
+    if (N > 0 && ((uintptr_t)state & 15u)) return fail(SIMAPS_EINVAL, "state %p is not aligned to 16 bytes", state);
+    return 0;
+}
+
+int simaps_get_state_as(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                        const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                        const float *overhead, void *state, int state_dtype, int num_robots_per_env,
+                        const simaps_debug *dbg, void *stream)
+{
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, state_dtype,
+                          num_robots_per_env, dbg, stream);
+}
+int simaps_ctx_get_state_as(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                            const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                            const uint8_t *occupancy, const float *overhead, void *state, int state_dtype,
+                            int num_robots_per_env, const simaps_debug *dbg, void *stream)
+{
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
+        state_dtype, num_robots_per_env, dbg, stream));
 }
 
 int simaps_get_state_mixed(const simaps_config *cfgs, const int32_t *num_robots_per_env, int n_cfgs, int N,

@@ -1,5 +1,5 @@
-"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h and
-include/simaps_action.h).
+"""ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
+include/simaps_action.h and include/simaps_state16.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -31,6 +31,7 @@ ENV_DTYPE = np.dtype([('receptacle_x', '<f8'), ('receptacle_y', '<f8'), ('has_re
                       ('robot_off', '<i4'), ('num_robots', '<i4'), ('reserved', '<i4')], align=True)
 ABI_VERSION = 8  # include/simaps.h SIMAPS_ABI_VERSION
 ACTION_ABI_VERSION = 1  # include/simaps_action.h SIMAPS_ACTION_ABI_VERSION
+STATE16_ABI_VERSION = 1  # include/simaps_state16.h SIMAPS_STATE16_ABI_VERSION
 MAX_MIXED = 8  # SIMAPS_MAX_MIXED
 AGENT_DTYPE = np.dtype([('env', '<i4'), ('robot', '<i4'), ('map_slot', '<i4')], align=True)
 assert ROBOT_DTYPE.itemsize == 72 and ENV_DTYPE.itemsize == 32 and AGENT_DTYPE.itemsize == 12
@@ -102,6 +103,20 @@ EXPORTED_CTX = CTX_MANAGEMENT + tuple('simaps_ctx_' + n for n in CTX_TWINS)
 EXPORTED_ACTION = ('simaps_action_abi_version', 'simaps_num_output_channels', 'simaps_store_new_action',
                    'simaps_ctx_store_new_action')
 ACTION_SHORTEST_PATH, ACTION_WRITE_BACK = 1, 2  # SIMAPS_ACTION_* flag bits
+
+# include/simaps_state16.h: the state stack rendered as bf16 / fp16 (with its context twin)
+EXPORTED_STATE16 = ('simaps_state16_abi_version', 'simaps_get_state_as', 'simaps_ctx_get_state_as')
+STATE_F32, STATE_BF16, STATE_F16 = 0, 1, 2  # SIMAPS_STATE_*
+STATE_DTYPES = {torch.float32: STATE_F32, torch.bfloat16: STATE_BF16, torch.float16: STATE_F16}
+
+
+def state_dtype_id(dtype):
+    """SIMAPS_STATE_* of a torch dtype; ValueError for any other than float32, bfloat16, float16."""
+    try:
+        return STATE_DTYPES[dtype]
+    except (KeyError, TypeError):
+        raise ValueError('state dtype %r: torch.float32, torch.bfloat16 or torch.float16' % (dtype,)) from None
+
 
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
            7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action'}
@@ -187,6 +202,17 @@ def _load(path=LIB_PATH):
         if va != ACTION_ABI_VERSION:
             raise ImportError('libsimaps action ABI version mismatch: %s has %d, this binding is %d'
                               % (path, va, ACTION_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_as'):  # (include/simaps_state16.h; absent only in an older revision's A/B build)
+        L.simaps_state16_abi_version.restype = i32
+        L.simaps_get_state_as.argtypes = [ctypes.POINTER(Config), i32, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                          ctypes.POINTER(Debug), vp]
+        L.simaps_get_state_as.restype = i32
+        L.simaps_ctx_get_state_as.argtypes = [vp] + list(L.simaps_get_state_as.argtypes)
+        L.simaps_ctx_get_state_as.restype = i32
+        vs = L.simaps_state16_abi_version()
+        if vs != STATE16_ABI_VERSION:
+            raise ImportError('libsimaps state16 ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vs, STATE16_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

@@ -359,8 +359,11 @@ class StateBatch(_ArrayUpload):
             return (n, self.C, K.LOCAL_MAP_PIXEL_WIDTH, K.LOCAL_MAP_PIXEL_WIDTH)
         return (n, K.LOCAL_MAP_PIXEL_WIDTH, K.LOCAL_MAP_PIXEL_WIDTH, self.C)
 
-    def alloc_state(self, n=None):
-        return torch.empty(self.out_shape(n), dtype=torch.float32, device=self.device)
+    def alloc_state(self, n=None, dtype=torch.float32):
+        """An output tensor for render(): float32, or torch.bfloat16 / torch.float16 (the stack rendered
+        directly in the narrow format, include/simaps_state16.h)."""
+        _lib.state_dtype_id(dtype)
+        return torch.empty(self.out_shape(n), dtype=dtype, device=self.device)
 
     def as_hwc(self, state):
         """The reference's (N, 96, 96, C) view of a rendered batch (zero-copy for the CHW layout)."""
@@ -373,16 +376,21 @@ class StateBatch(_ArrayUpload):
         return {'cspace': z(n, h, w, dt=torch.uint8), 'sources': z(n, 2, 4, dt=torch.int32),
                 'dist': z(n, 2, h, w, dt=torch.float32), 'status': z(n, dt=torch.int32)}
 
-    def render(self, out=None, debug=None, stream=None, slots=None):
+    def render(self, out=None, debug=None, stream=None, slots=None, dtype=None):
         """Launch the fused kernel: the stacks of every agent (or of map slots `slots`, in that
         order) into `out` (allocated if None).  Asynchronous on `stream` (default: the current
-        stream); with a side stream, wait for it before reading `out` on another stream."""
+        stream); with a side stream, wait for it before reading `out` on another stream.
+        The element type is out.dtype -- float32, or bfloat16 / float16: each value rounded to nearest
+        even where the kernel stores it, bit for bit render().to(dtype) without the cast pass
+        (simaps_get_state_as); `dtype` chooses it when render() allocates (default float32)."""
         agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
         if out is None:
-            out = self.alloc_state(n)
-        if not (out.is_contiguous() and tuple(out.shape) == self.out_shape(n) and out.dtype == torch.float32
-                and out.device == self.device):
-            raise ValueError('out must be a contiguous float32 %s tensor on %s' % (self.out_shape(n), self.device))
+            out = self.alloc_state(n, torch.float32 if dtype is None else dtype)
+        elif dtype is not None and dtype != out.dtype:
+            raise ValueError('dtype %s given with an out tensor of %s' % (dtype, out.dtype))
+        dtype_id = _lib.state_dtype_id(out.dtype)
+        if not (out.is_contiguous() and tuple(out.shape) == self.out_shape(n) and out.device == self.device):
+            raise ValueError('out must be a contiguous %s tensor on %s' % (self.out_shape(n), self.device))
         if n == 0:
             return out
         dbg = None
@@ -397,10 +405,15 @@ class StateBatch(_ArrayUpload):
         s, cur = launch_stream(self.device, stream)
         if rec is not None:
             self._rec_wait(s)
-        _lib.check(_lib.call(self.context, 'get_state', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
-            _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
-            _lib.ptr(out), self.num_robots if self.flags['use_intention_channels'] else 0,
-            None if dbg is None else dbg, _lib.stream_handle(s)))
+        nrpe = self.num_robots if self.flags['use_intention_channels'] else 0
+        if dtype_id == _lib.STATE_F32:
+            _lib.check(_lib.call(self.context, 'get_state', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+                _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
+                _lib.ptr(out), nrpe, None if dbg is None else dbg, _lib.stream_handle(s)))
+        else:
+            _lib.check(_lib.call(self.context, 'get_state_as', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+                _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
+                _lib.ptr(out), dtype_id, nrpe, None if dbg is None else dbg, _lib.stream_handle(s)))
         hold(s, cur, out, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, self.overhead, rec,
              *(debug.values() if debug else ()))
         if rec is not None:

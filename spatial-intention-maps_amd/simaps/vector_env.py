@@ -41,7 +41,7 @@ class VectorEnvObservations:
     (C, 96, 96) planes (what a conv policy consumes, policies.py:44-45) -- states returned by
     get_state() are always the reference's (96, 96, C) index order (views for 'chw')."""
 
-    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0, context=None):
+    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0, context=None, dtype=torch.float32):
         """reuse_outputs=R > 0: all-robots get_state() renders into a ring of R preallocated output
         batches and returns a structure of views built once per ring slot (no per-call allocation
         or per-robot view creation: ~0.2 ms of host time per 256 stacks).  The states of a call are
@@ -50,7 +50,13 @@ class VectorEnvObservations:
         host copy: one asynchronous device->host copy per call into page-locked memory, returned as
         NumPy views (a fresh pageable copy per call otherwise).
         context: a simaps.context.Context that every launch and fault check of this object goes
-        through (None: the process-wide default context)."""
+        through (None: the process-wide default context).
+        dtype: torch.float32 (the reference's), or torch.bfloat16 / torch.float16: every state is
+        rendered directly in that format (StateBatch.render(dtype=...)), the ring and the pinned host
+        copies included.  numpy=True returns float16 states as np.float16; NumPy has no bfloat16, so
+        get_state(numpy=True) with torch.bfloat16 raises ValueError."""
+        _lib.state_dtype_id(dtype)
+        self.dtype = dtype
         self.batch = _batch.StateBatch(scenes, device=device, layout=layout, context=context)
         self._ring = [None] * int(reuse_outputs)
         self._ring_k = 0
@@ -93,7 +99,7 @@ class VectorEnvObservations:
     # -- VectorEnv.get_state ---------------------------------------------------------------------
     def get_state(self, all_robots=False, awaiting=None, save_figures=False, numpy=False, stream=None,
                   figures_dir='figures', occupancy_maps=None):
-        """[env][group][robot] -> (96, 96, C) float32 state, or None for robots not awaiting a new
+        """[env][group][robot] -> (96, 96, C) state (float32, or the constructor's dtype), or None for robots not awaiting a new
         action (envs.py:322-323).  awaiting: per env, per robot truthy flags
         (robot.awaiting_new_action); None means every robot.  numpy=True returns host NumPy arrays
         like the reference (one device->host copy for the whole batch); otherwise device tensors.
@@ -103,13 +109,16 @@ class VectorEnvObservations:
         maps (simaps.figures; env.png, the simulator's camera image, is not written).  occupancy_maps:
         {(env, robot): OccupancyMap(show_map=True)}, the env.show_occupancy_maps case (envs.py:2180-2182):
         each figured robot's map figure is saved there as global-occupancy-map.png."""
+        if numpy and self.dtype == torch.bfloat16:
+            raise ValueError('numpy=True with dtype=torch.bfloat16: NumPy has no bfloat16 (take device tensors, or '
+                             'torch.float16 / torch.float32 states)')
         if save_figures:
             return self._get_state_with_figures(all_robots, awaiting, numpy, stream, figures_dir, occupancy_maps)
         if (all_robots or awaiting is None) and self._ring and not numpy:
             k = self._ring_k
             self._ring_k = (k + 1) % len(self._ring)
             if self._ring[k] is None:
-                buf = self.batch.alloc_state()
+                buf = self.batch.alloc_state(dtype=self.dtype)
                 rows = self.batch.as_hwc(buf).unbind(0)
                 self._ring[k] = (buf, [[[rows[q] for q in g] for g in env] for env in self._all_slots])
             buf, views = self._ring[k]
@@ -119,7 +128,7 @@ class VectorEnvObservations:
             k = self._hring_k
             self._hring_k = (k + 1) % len(self._hring)
             if self._hring[k] is None:
-                buf = self.batch.alloc_state()
+                buf = self.batch.alloc_state(dtype=self.dtype)
                 host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
                 rows = self.batch.as_hwc(host).numpy()
                 self._hring[k] = (buf, host, [[[rows[q] for q in g] for g in env] for env in self._all_slots])
@@ -132,7 +141,7 @@ class VectorEnvObservations:
             _lib.check_context_faults(self.batch.context)  # the copy completed: a faulting launch raises here
             return views
         if all_robots or awaiting is None:  # every robot: the batch's own agent list, structure precomputed
-            out = self.batch.as_hwc(self.batch.render(stream=stream))
+            out = self.batch.as_hwc(self.batch.render(stream=stream, dtype=self.dtype))
             if numpy:
                 if stream is not None:
                     torch.cuda.current_stream(self.batch.device).wait_stream(stream)
@@ -145,7 +154,7 @@ class VectorEnvObservations:
             for a in range(len(s['robots'])):
                 if awaiting[e][a]:
                     want.append(self.slot[(e, a)])
-        out = self.batch.as_hwc(self.batch.render(slots=want, stream=stream))
+        out = self.batch.as_hwc(self.batch.render(slots=want, stream=stream, dtype=self.dtype))
         if numpy:
             if stream is not None:
                 torch.cuda.current_stream(self.batch.device).wait_stream(stream)
@@ -179,7 +188,7 @@ class VectorEnvObservations:
             rid = s['robots'][a].get('id', '%d_%d' % (e, a))
             out = os.path.join(figures_dir, 'robot_id_{}'.format(rid))
             figures.save_state_figures(out, s['flags'], s['room_length'], s['room_width'], len(s['robots']),
-                                       st if numpy else st.cpu().numpy(), gm)
+                                       st if numpy else st.float().cpu().numpy(), gm)
             if occupancy_maps and (e, a) in occupancy_maps:
                 occupancy_maps[(e, a)].save_figure(os.path.join(out, 'global-occupancy-map.png'))
         return states

@@ -10,6 +10,9 @@
   store_new_action (--action) the step back from the policy (simaps_store_new_action): device time
                  of the call and of its decode kernel, and the wall time per step against the same
                  result composed from torch arg-max + numpy + shortest_paths + set_descriptor_arrays
+  state16        (--state16) the state stack rendered directly as bf16 / fp16 (simaps_get_state_as)
+                 against the float32 render and the float32 render + cast pass: device time per
+                 256 stacks, the four alternating in one process
   gridgraph_large (--gridgraph-large) GridGraph on a 500 x 500 grid (beyond the LDS window: the
                  global-memory kernels of csrc/grid_large.h): images and paths, 1 and 64 per call
 
@@ -351,6 +354,68 @@ def bench_action(args):
         f.write(''.join(json.dumps(x) + '\n' for x in lines))
 
 
+def bench_state16(args):
+    """The render launch of `envs` envs of `config` (BASELINE configs[1]: 256 stacks), CHW, as
+    (a) float32, (b) float32 + the cast pass a 16-bit consumer needs today (copy_ into a preallocated
+    bfloat16 batch), (c) bfloat16 and (d) float16 written by the fused kernel.  Device time by HIP
+    events around `reps` calls queued behind a blocking kernel (so the events see the device and not
+    the host's per-call time); the four variants alternate round by round in this process, and each
+    reports its rounds' median, min and max.  (c) and (d) do (a)'s work with fewer bytes written, so
+    they are expected within (a)'s own min..max of this session or below; (b) - (c) is the gain."""
+    scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
+    b = batch.StateBatch(scenes, layout='chw')
+    f32 = b.alloc_state()
+    o16 = {dt: b.alloc_state(dtype=dt) for dt in (torch.bfloat16, torch.float16)}
+    cast = b.alloc_state(dtype=torch.bfloat16)
+
+    def render_and_cast():
+        b.render(out=f32)
+        cast.copy_(f32)
+    variants = {'a_f32': lambda: b.render(out=f32), 'b_f32_plus_cast_bf16': render_and_cast,
+                'c_bf16': lambda: b.render(out=o16[torch.bfloat16]), 'd_f16': lambda: b.render(out=o16[torch.float16])}
+    for f in variants.values():
+        for _ in range(20):
+            f()
+    torch.cuda.synchronize()
+    assert torch.equal(o16[torch.bfloat16], cast) and torch.equal(o16[torch.float16], f32.to(torch.float16))
+    big = torch.randn(8192, 8192, device='cuda')
+    s = torch.cuda.current_stream()
+    us = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for name, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.mm(big, big)
+            torch.mm(big, big)
+            e0.record(s)
+            for _ in range(args.reps):
+                f()
+            e1.record(s)
+            torch.cuda.synchronize()
+            us[name].append(e0.elapsed_time(e1) / args.reps * 1e3)
+    from simaps import _lib
+    _lib.check_faults()
+    a_lo, a_hi = min(us['a_f32']), max(us['a_f32'])
+    elems = b.N * b.C * 96 * 96
+    lines = []
+    for name, v in us.items():
+        line = {'row': 'state16', 'variant': name, 'config': args.config, 'stacks': b.N, 'channels': b.C, 'layout': 'chw',
+                'median_us': float(np.median(v)), 'min_us': min(v), 'max_us': max(v), 'rounds_us': [round(x, 3) for x in v],
+                'state_bytes_written': elems * (4 if name.startswith(('a_', 'b_')) else 2),
+                'cast_pass_bytes': elems * 6 if name.startswith('b_') else 0, 'reps_per_round': args.reps}
+        if name in ('c_bf16', 'd_f16'):
+            line['a_spread_us'] = [a_lo, a_hi]
+            line['median_within_or_below_a_spread'] = bool(np.median(v) <= a_hi)
+        if name == 'c_bf16':
+            line['gain_over_b_us'] = float(np.median(us['b_f32_plus_cast_bf16']) - np.median(v))
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    lines.append({'row': 'state16_note', 'note': 'device time per call: HIP events around reps_per_round calls queued '
+                  'behind two 8192^3 float32 matmuls, after 20 warm-up calls per variant; the variants alternate round '
+                  'by round in one process; b = float32 render + copy_ into a preallocated bfloat16 batch'})
+    with open(args.out, 'w') as f:
+        f.write(''.join(json.dumps(x) + '\n' for x in lines))
+
+
 def bench_remap(args):
     """The periodic re-map of one moving robot (RobotController.step -> update_map every 200
     simulation steps, envs.py:1401-1403): a single-frame simaps_ingest, end to end (host prep +
@@ -526,6 +591,16 @@ if __name__ == '__main__':
         sys.exit(0)
     if '--gridgraph-large' in sys.argv:
         bench_gridgraph_large()
+        sys.exit(0)
+    if '--state16' in sys.argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument('--state16', action='store_true')
+        ap.add_argument('--config', default='lifting_4-small_divider')
+        ap.add_argument('--envs', type=int, default=64)
+        ap.add_argument('--rounds', type=int, default=15)
+        ap.add_argument('--reps', type=int, default=100)
+        ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'state16_bench.jsonl'))
+        bench_state16(ap.parse_args())
         sys.exit(0)
     if '--action' in sys.argv:
         bench_action(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, awaiting=(64, 256)))
