@@ -54,7 +54,8 @@ typedef struct simaps_ctx simaps_ctx; /* opaque */
 #define SIMAPS_K_OCCUPANCY_MAP 10  /* build_cspace / snap_sources twins: agent n */
 #define SIMAPS_K_GLOBAL_MAPS 11    /* global_maps twin: agent n */
 #define SIMAPS_K_ACTION 12         /* store_new_action twin (simaps_action.h), the decode kernel: agent n */
-#define SIMAPS_K_COUNT 12
+#define SIMAPS_K_GET_STATE_INTO 13  /* get_state_into twin (simaps_store.h): agent n */
+#define SIMAPS_K_COUNT 13
 
 /* A new context on device `device` (>= 0: that ordinal; -1: the calling thread's current device),
  * with its own 64-byte host-mapped fault record, path mode 0 and (on first use) its own memory pool.

@@ -12,7 +12,8 @@
  * a float32 subnormal converts like any other value: bit for bit tensor.to(torch.bfloat16 /
  * torch.float16) of the float32 stack.  NaN inputs are unspecified (states contain none).
  *
- * Not covered: simaps_get_state_mixed stays float32.
+ * Not covered here: simaps_get_state_mixed stays float32; its 16-bit form is simaps_get_state_mixed_as
+ * (simaps_store.h).
  */
 #ifndef SIMAPS_STATE16_H
 #define SIMAPS_STATE16_H

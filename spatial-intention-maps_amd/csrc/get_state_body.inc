@@ -3,7 +3,9 @@
 // offset come from the launch's tables (simaps_get_state_mixed) instead of the launch-wide arguments.
 // (A textual include rather than a template: get_state_kernel's source, and so its code, stay
 // exactly those of the single-configuration kernel.)  With SIMAPS_STATE16 (simaps_state16.inc) state
-// is the 16-bit stack and RenderCtx converts at the store; nothing else differs.
+// is the 16-bit stack and RenderCtx converts at the store; nothing else differs.  With GS_INTO
+// (simaps_store.inc, GS_MIXED 0) the stack goes to row into_row of the caller's store and faults are
+// posted under SIMAPS_K_GET_STATE_INTO.
 #if defined(SIMAPS_VGPR_CAP) && !GS_MIXED  // (timing-only A/B build: the LDS hidden from the occupancy estimate)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #else
@@ -55,8 +57,12 @@
     lds_barrier();  // the group barriers are zeroed
     if (tid == 0 && bad_desc) sh.bar[0][3] = 1u;
     if (tid == 0) STAMP_NB(0);
-#if GS_MIXED
+#if GS_MIXED && defined(SIMAPS_STATE16)  // (simaps_store.inc: the mixed launch's 16-bit stack, out_off in elements)
+    uint16_t *out = state + (size_t)out_off[n];
+#elif GS_MIXED
     float *out = state + (size_t)out_off[n];
+#elif defined(GS_INTO)  // (simaps_store.inc: row into_row of the caller's store, a 64-bit offset onto the base)
+    auto *out = state + (size_t)into_row * LW * LW * C;
 #elif defined(SIMAPS_STATE16)
     uint16_t *out = state + (size_t)n * LW * LW * C;
 #else
@@ -222,7 +228,11 @@
     }
     if (tid == 0) {
         const unsigned f = group_faults(sh.bar, sh.rounds, nsrc);
+#ifdef GS_INTO
+        post_faults(fault, f, SIMAPS_K_GET_STATE_INTO, n);
+#else
         post_faults(fault, f, GS_MIXED ? SIMAPS_K_GET_STATE_MIXED : SIMAPS_K_GET_STATE, n);
+#endif
         if (dbg.status) {
             int st = (f & SIMAPS_FAULT_ROUNDS ? 2 : 0) | (f & SIMAPS_FAULT_TIMEOUT ? 4 : 0) |
                      (f & SIMAPS_FAULT_DESCRIPTOR ? 8 : 0);

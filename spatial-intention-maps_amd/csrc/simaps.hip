@@ -48,7 +48,9 @@
 #include "mixed.h"
 #include "simaps_action.h"  // (includes simaps_ctx.h, which includes simaps.h)
 #include "simaps_state16.h"
+#include "simaps_store.h"
 #include "state16.h"
+#include "store.h"
 
 using namespace simaps;
 
@@ -4265,7 +4267,7 @@ const char *kernel_name(unsigned id)
 {
     static const char *const names[SIMAPS_K_COUNT + 1] = {
         "?", "get_state", "get_state_mixed", "sp_distance", "path", "sssp_grid", "grid_path", "gl_sssp", "gl_tile",
-        "gl_path", "occupancy_map", "global_maps", "action"};
+        "gl_path", "occupancy_map", "global_maps", "action", "get_state_into"};
     return id <= SIMAPS_K_COUNT ? names[id] : "?";
 }
 
@@ -4579,8 +4581,11 @@ int simaps_robot_mask(int type, int with_cube, float *out)
 static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
                           const simaps_env *envs,
                      const simaps_robot *robots, const double *paths, const uint8_t *occupancy, const float *overhead,
-                     void *state, int state_dtype, int num_robots_per_env, const simaps_debug *dbg, void *stream)
+                     void *state, int state_dtype, int num_robots_per_env, const simaps_debug *dbg, void *stream,
+                     const int64_t *dest = nullptr, int64_t capacity = 0)
 {
+    // dest != nullptr: simaps_get_state_into (simaps_store.h) -- `state` is the caller's store of
+    // `capacity` stacks (NULL allowed with capacity 0: check_state_into) and dest[n] agent n's row
     int rc = check_cfg(cfg);
     const Geometry &geo = geometry();
     for (int t = 0; t < 4; t++)
@@ -4588,7 +4593,8 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     if (rc) return rc;
     if (N < 0) return fail(SIMAPS_EINVAL, "N < 0");
     if (N == 0) return 0;
-    if (!agents || !envs || !robots || !occupancy || !overhead || !state) return fail(SIMAPS_EINVAL, "NULL buffer");
+    if (!agents || !envs || !robots || !occupancy || !overhead || (!state && !dest))
+        return fail(SIMAPS_EINVAL, "NULL buffer");
     if ((cfg->use_intention_map || cfg->use_history_map) && !paths) return fail(SIMAPS_EINVAL, "paths is NULL");
     if (cfg->use_intention_channels && (num_robots_per_env < 1 || num_robots_per_env > SIMAPS_MAX_ROBOTS))
         return fail(SIMAPS_EINVAL, "intention channels need num_robots_per_env in [1, %d]", SIMAPS_MAX_ROBOTS);
@@ -4597,6 +4603,20 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     simaps_debug d;
     memset(&d, 0, sizeof(d));
     if (dbg) d = *dbg;
+    if (dest) {  // simaps_get_state_into: one launch of the element type's kernel (simaps_store.inc)
+        if (state_dtype == SIMAPS_STATE_F32)
+            simaps_store::launch_get_state_into_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
+                                                    (float *)state, capacity, dest, C, d, cx.fault_dev,
+                                                    (hipStream_t)stream);
+        else
+            (state_dtype == SIMAPS_STATE_BF16 ? simaps_store::launch_get_state_into_bf16
+                                              : simaps_store::launch_get_state_into_f16)(
+                *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity, dest, C, d,
+                cx.fault_dev, (hipStream_t)stream);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_into launch: %s", hipGetErrorString(e));
+        return 0;
+    }
     if (state_dtype != SIMAPS_STATE_F32) {  // simaps_get_state_as: the 16-bit instantiations (simaps_state16.inc)
         (state_dtype == SIMAPS_STATE_BF16 ? simaps_state16::launch_get_state_bf16 : simaps_state16::launch_get_state_f16)(
             *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, C, d, cx.fault_dev,
@@ -4624,8 +4644,8 @@ static int get_state_mixed_impl(simaps_ctx &cx, const simaps_config *cfgs, const
                                 int n_cfgs, int N,
                            const simaps_agent *agents, const int32_t *agent_cfg, const simaps_env *envs,
                            const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                           const int64_t *map_off, const float *overhead, float *state, const int64_t *out_off,
-                           void *stream)
+                           const int64_t *map_off, const float *overhead, void *state, const int64_t *out_off,
+                           void *stream, int state_dtype = SIMAPS_STATE_F32)
 {
     if (!cfgs || n_cfgs < 1 || n_cfgs > SIMAPS_MAX_MIXED)
         return fail(SIMAPS_EINVAL, "n_cfgs %d not in [1, %d]", n_cfgs, SIMAPS_MAX_MIXED);
@@ -4652,8 +4672,14 @@ static int get_state_mixed_impl(simaps_ctx &cx, const simaps_config *cfgs, const
         return fail(SIMAPS_EINVAL, "NULL buffer");
     if (any_paths && !paths) return fail(SIMAPS_EINVAL, "paths is NULL");
     if (const int rc = pending_faults(cx)) return rc;
-    simaps_mixed::launch_get_state_mixed(mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off, overhead,
-                                         state, out_off, cx.fault_dev, (hipStream_t)stream);
+    if (state_dtype != SIMAPS_STATE_F32)  // simaps_get_state_mixed_as: the 16-bit instantiations (simaps_store.inc)
+        (state_dtype == SIMAPS_STATE_BF16 ? simaps_store::launch_get_state_mixed_bf16
+                                          : simaps_store::launch_get_state_mixed_f16)(
+            mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off, overhead, (uint16_t *)state, out_off,
+            cx.fault_dev, (hipStream_t)stream);
+    else
+        simaps_mixed::launch_get_state_mixed(mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off,
+                                             overhead, (float *)state, out_off, cx.fault_dev, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_mixed launch: %s", hipGetErrorString(e));
     return 0;
@@ -5187,6 +5213,65 @@ int simaps_ctx_get_state_mixed(simaps_ctx *ctx, const simaps_config *cfgs, const
 {
     SIMAPS_ON_CTX(ctx, get_state_mixed_impl(cx, cfgs, num_robots_per_env, n_cfgs, N, agents, agent_cfg, envs, robots,
         paths, occupancy, map_off, overhead, state, out_off, stream));
+}
+
+// ---- simaps_store.h
+int simaps_store_abi_version(void) { return SIMAPS_STORE_ABI_VERSION; }
+
+// what simaps_get_state_into checks on top of simaps_get_state (N <= 0 is get_state_impl's to answer)
+static int check_state_into(int N, const void *store, int state_dtype, int64_t capacity, const int64_t *dest)
+{
+    if (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16)
+        return fail(SIMAPS_EINVAL, "unknown state_dtype %d (SIMAPS_STATE_F32, _BF16 or _F16)", state_dtype);
+    if (capacity < 0) return fail(SIMAPS_EINVAL, "capacity %lld < 0", (long long)capacity);
+    if (N > 0 && !dest) return fail(SIMAPS_EINVAL, "dest is NULL");
+    if (N > 0 && capacity > 0 && !store) return fail(SIMAPS_EINVAL, "store is NULL");
+    if (N > 0 && capacity > 0 && ((uintptr_t)store & 15u))
+        return fail(SIMAPS_EINVAL, "store %p is not aligned to 16 bytes", store);
+    return 0;
+}
+
+int simaps_get_state_into(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                          const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                          const float *overhead, void *store, int state_dtype, int64_t capacity, const int64_t *dest,
+                          int num_robots_per_env, const simaps_debug *dbg, void *stream)
+{
+    if (const int rc = check_state_into(N, store, state_dtype, capacity, dest)) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, store, state_dtype,
+                          num_robots_per_env, dbg, stream, dest, capacity);
+}
+int simaps_ctx_get_state_into(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                              const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                              const uint8_t *occupancy, const float *overhead, void *store, int state_dtype,
+                              int64_t capacity, const int64_t *dest, int num_robots_per_env, const simaps_debug *dbg,
+                              void *stream)
+{
+    if (const int rc = check_state_into(N, store, state_dtype, capacity, dest)) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, store,
+        state_dtype, num_robots_per_env, dbg, stream, dest, capacity));
+}
+
+int simaps_get_state_mixed_as(const simaps_config *cfgs, const int32_t *num_robots_per_env, int n_cfgs, int N,
+                              const simaps_agent *agents, const int32_t *agent_cfg, const simaps_env *envs,
+                              const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                              const int64_t *map_off, const float *overhead, void *state, const int64_t *out_off,
+                              int state_dtype, void *stream)
+{
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_mixed_impl(cx, cfgs, num_robots_per_env, n_cfgs, N, agents, agent_cfg, envs, robots, paths,
+                                occupancy, map_off, overhead, state, out_off, stream, state_dtype);
+}
+int simaps_ctx_get_state_mixed_as(simaps_ctx *ctx, const simaps_config *cfgs, const int32_t *num_robots_per_env,
+                                  int n_cfgs, int N, const simaps_agent *agents, const int32_t *agent_cfg,
+                                  const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                                  const uint8_t *occupancy, const int64_t *map_off, const float *overhead, void *state,
+                                  const int64_t *out_off, int state_dtype, void *stream)
+{
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_mixed_impl(cx, cfgs, num_robots_per_env, n_cfgs, N, agents, agent_cfg, envs, robots,
+        paths, occupancy, map_off, overhead, state, out_off, stream, state_dtype));
 }
 
 int simaps_sp_distance(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,

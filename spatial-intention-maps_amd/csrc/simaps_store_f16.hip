@@ -1,0 +1,3 @@
+// The fp16 kernels of include/simaps_store.h (simaps_store.inc), a translation unit of their own.
+#define SIMAPS_STORE_DTYPE 2
+#include "simaps_store.inc"

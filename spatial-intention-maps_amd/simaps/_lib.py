@@ -1,5 +1,5 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
-include/simaps_action.h and include/simaps_state16.h).
+include/simaps_action.h, include/simaps_state16.h and include/simaps_store.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -32,6 +32,7 @@ ENV_DTYPE = np.dtype([('receptacle_x', '<f8'), ('receptacle_y', '<f8'), ('has_re
 ABI_VERSION = 8  # include/simaps.h SIMAPS_ABI_VERSION
 ACTION_ABI_VERSION = 1  # include/simaps_action.h SIMAPS_ACTION_ABI_VERSION
 STATE16_ABI_VERSION = 1  # include/simaps_state16.h SIMAPS_STATE16_ABI_VERSION
+STORE_ABI_VERSION = 1  # include/simaps_store.h SIMAPS_STORE_ABI_VERSION
 MAX_MIXED = 8  # SIMAPS_MAX_MIXED
 AGENT_DTYPE = np.dtype([('env', '<i4'), ('robot', '<i4'), ('map_slot', '<i4')], align=True)
 assert ROBOT_DTYPE.itemsize == 72 and ENV_DTYPE.itemsize == 32 and AGENT_DTYPE.itemsize == 12
@@ -118,8 +119,15 @@ def state_dtype_id(dtype):
         raise ValueError('state dtype %r: torch.float32, torch.bfloat16 or torch.float16' % (dtype,)) from None
 
 
+# include/simaps_store.h: states rendered into a caller-owned store at device-chosen rows, and the
+# mixed launch in bf16 / fp16 (each with its context twin)
+EXPORTED_STORE = ('simaps_store_abi_version', 'simaps_get_state_into', 'simaps_ctx_get_state_into',
+                  'simaps_get_state_mixed_as', 'simaps_ctx_get_state_mixed_as')
+
+
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
-           7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action'}
+           7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action',
+           13: 'get_state_into'}
 
 
 def _load(path=LIB_PATH):
@@ -213,6 +221,23 @@ def _load(path=LIB_PATH):
         if vs != STATE16_ABI_VERSION:
             raise ImportError('libsimaps state16 ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vs, STATE16_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_into'):  # (include/simaps_store.h; absent only in an older revision's A/B build)
+        L.simaps_store_abi_version.restype = i32
+        # simaps_get_state_as's list with capacity and dest after state_dtype
+        L.simaps_get_state_into.argtypes = [ctypes.POINTER(Config), i32, vp, vp, vp, vp, vp, vp, vp, i32,
+                                            ctypes.c_int64, vp, i32, ctypes.POINTER(Debug), vp]
+        L.simaps_get_state_into.restype = i32
+        L.simaps_ctx_get_state_into.argtypes = [vp] + list(L.simaps_get_state_into.argtypes)
+        L.simaps_ctx_get_state_into.restype = i32
+        # simaps_get_state_mixed's list with state_dtype before stream
+        L.simaps_get_state_mixed_as.argtypes = list(L.simaps_get_state_mixed.argtypes[:-1]) + [i32, vp]
+        L.simaps_get_state_mixed_as.restype = i32
+        L.simaps_ctx_get_state_mixed_as.argtypes = [vp] + list(L.simaps_get_state_mixed_as.argtypes)
+        L.simaps_ctx_get_state_mixed_as.restype = i32
+        vt = L.simaps_store_abi_version()
+        if vt != STORE_ABI_VERSION:
+            raise ImportError('libsimaps store ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vt, STORE_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

@@ -423,6 +423,79 @@ class StateBatch(_ArrayUpload):
             self._rec_ver[sl] = self._map_ver[sl]
         return out
 
+    def alloc_store(self, capacity, dtype=torch.float32):
+        """A store of `capacity` stacks for render_into(): [capacity, C, 96, 96] (layout 'chw') or
+        [capacity, 96, 96, C], float32, bfloat16 or float16.  Uninitialised."""
+        _lib.state_dtype_id(dtype)
+        if int(capacity) < 0:
+            raise ValueError('capacity %d < 0' % capacity)
+        return torch.empty(self.out_shape(int(capacity)), dtype=dtype, device=self.device)
+
+    def render_into(self, store, dest, slots=None, debug=None, stream=None):
+        """Launch the fused kernel with each agent's stack going to a row of the caller's `store`
+        chosen by `dest` (simaps_get_state_into, include/simaps_store.h): agent n (of every agent, or
+        of map slots `slots`, in that order) is rendered into store[dest[n]], and not rendered at all
+        where dest[n] == -1.  One launch, no copy pass; returns `store`.
+
+        store: contiguous, on the batch's device, float32 / bfloat16 / float16 (values as render()
+        gives them in that dtype), of shape (capacity,) + out_shape()[1:] -- e.g. alloc_store().
+        dest: an int64 device tensor of length n, used as it is and never read on the host: the call
+        stays asynchronous and can be captured in a graph whose replays follow whatever a kernel
+        wrote into `dest` before them.  Its non-negative values must be distinct (two agents with one
+        row race); a value outside [-1, capacity) posts a descriptor fault (kernel 'get_state_into')
+        and writes nothing.  Or a host sequence of ints: checked here for length, range and
+        duplicates (ValueError), then uploaded.
+
+        The receptacle distance cache is not passed to this launch and its versions are left alone:
+        the host cannot know which agents a device-side `dest` rendered.  debug outputs are indexed
+        by n as in render(); a skipped agent's rows are not written."""
+        agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
+        if not isinstance(store, torch.Tensor):
+            raise ValueError('store must be a tensor')
+        try:
+            dtype_id = _lib.state_dtype_id(store.dtype)
+        except ValueError:
+            raise ValueError('store dtype %s: torch.float32, torch.bfloat16 or torch.float16' % store.dtype) from None
+        row = self.out_shape(0)[1:]
+        if not (store.dim() == 4 and tuple(store.shape[1:]) == row and store.is_contiguous()
+                and store.device == self.device):
+            raise ValueError('store must be a contiguous (capacity,) + %s tensor on %s' % (row, self.device))
+        capacity = store.shape[0]
+        if isinstance(dest, torch.Tensor):
+            if not (dest.dtype == torch.int64 and dest.device == self.device and dest.dim() == 1
+                    and dest.shape[0] == n and dest.is_contiguous()):
+                raise ValueError('dest must be a contiguous int64 tensor of length %d on %s' % (n, self.device))
+        else:
+            try:
+                host = np.asarray([int(d) for d in dest], dtype=np.int64)
+            except TypeError:
+                raise ValueError('dest must be an int64 device tensor or a sequence of ints') from None
+            if len(host) != n:
+                raise ValueError('dest has %d entries for %d agents' % (len(host), n))
+            if len(host) and (host.min() < -1 or host.max() >= capacity):
+                raise ValueError('dest %d outside [0, %d) (-1 skips an agent)'
+                                 % (int(host[(host < -1) | (host >= capacity)][0]), capacity))
+            rows = host[host >= 0]
+            if len(np.unique(rows)) != len(rows):
+                raise ValueError('dest names a row of the store more than once')
+            dest = torch.from_numpy(host).to(self.device)
+        if n == 0:
+            return store
+        dbg = None
+        if debug is not None:
+            for k, v in debug.items():
+                if v is not None and (v.shape[0] != n or not v.is_contiguous() or v.device != self.device):
+                    raise ValueError('debug[%r] must be contiguous with leading dim %d on %s' % (k, n, self.device))
+            dbg = _lib.Debug(*(debug[k].data_ptr() if debug.get(k) is not None else None
+                               for k in ('cspace', 'sources', 'dist', 'status')), None)
+        s, cur = launch_stream(self.device, stream)
+        nrpe = self.num_robots if self.flags['use_intention_channels'] else 0
+        _lib.check(_lib.call(self.context, 'get_state_into', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+            _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
+            _lib.ptr(store), dtype_id, capacity, _lib.ptr(dest), nrpe, dbg, _lib.stream_handle(s)))
+        hold(s, cur, store, dest, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, self.overhead,
+             *(debug.values() if debug else ()))
+        return store
 
     def shortest_path_distances(self, sources, targets, slots=None, stream=None, _rec=None):
         """OccupancyMap.shortest_path_distance(source, target) (envs.py:2507-2512) on each agent's own
@@ -984,7 +1057,8 @@ class MixedStateBatch(_ArrayUpload):
     channels the robot count; at most _lib.MAX_MIXED) rendered in ONE launch (simaps_get_state_mixed)
     -- e.g. the envs of collectors of different configurations (the reference's collector runs all
     its workers on one, train_multiprocess.py:159-166, 217-228).  Every agent of every scene
-    is a map slot, in scene order.  render() returns one flat float32 tensor; states() gives each
+    is a map slot, in scene order.  render() returns one flat tensor (float32, or bfloat16 / float16 with
+    dtype=); states() gives each
     agent's (C, 96, 96) (layout 'chw') or (96, 96, C) ('hwc') view of it, C that of its own
     configuration.  The results equal one StateBatch.render per configuration, bit for bit."""
 
@@ -1022,22 +1096,36 @@ class MixedStateBatch(_ArrayUpload):
         self.scenes = scenes
         self.robots_d, self.envs_d, self.agents_d, self.paths_d = (_to_dev(x, self.device) for x in (robots, envs, ag, paths))
 
-    def alloc_state(self):
-        return torch.empty((self.plan['out_numel'],), dtype=torch.float32, device=self.device)
+    def alloc_state(self, dtype=torch.float32):
+        """The flat output tensor of render(): float32, or torch.bfloat16 / torch.float16."""
+        _lib.state_dtype_id(dtype)
+        return torch.empty((self.plan['out_numel'],), dtype=dtype, device=self.device)
 
-    def render(self, out=None, stream=None):
-        """One launch for every agent; asynchronous on `stream` (default: the current stream)."""
+    def render(self, out=None, stream=None, dtype=None):
+        """One launch for every agent; asynchronous on `stream` (default: the current stream).
+        The element type is out.dtype -- float32, or bfloat16 / float16, each value rounded to nearest
+        even where the kernel stores it, bit for bit render().to(dtype) (simaps_get_state_mixed_as,
+        include/simaps_store.h); `dtype` chooses it when render() allocates (default float32)."""
         if out is None:
-            out = self.alloc_state()
-        if not (out.is_contiguous() and out.dtype == torch.float32 and out.numel() == self.plan['out_numel']
-                and out.device == self.device):
-            raise ValueError('out must be a contiguous float32 tensor of %d elements on %s' % (self.plan['out_numel'], self.device))
+            out = self.alloc_state(torch.float32 if dtype is None else dtype)
+        elif dtype is not None and dtype != out.dtype:
+            raise ValueError('dtype %s given with an out tensor of %s' % (dtype, out.dtype))
+        dtype_id = _lib.state_dtype_id(out.dtype)
+        if not (out.is_contiguous() and out.numel() == self.plan['out_numel'] and out.device == self.device):
+            raise ValueError('out must be a contiguous tensor of %d elements on %s' % (self.plan['out_numel'], self.device))
         s, cur = launch_stream(self.device, stream)
-        _lib.check(_lib.call(self.context, 'get_state_mixed', self._cfgs, self._nrs.ctypes.data,
-            len(self.plan['cfgs']), self.N, _lib.ptr(self.agents_d), _lib.ptr(self.agent_cfg_d),
-            _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy),
-            _lib.ptr(self.map_off_d), _lib.ptr(self.overhead), _lib.ptr(out), _lib.ptr(self.out_off_d),
-            _lib.stream_handle(s)))
+        if dtype_id == _lib.STATE_F32:
+            _lib.check(_lib.call(self.context, 'get_state_mixed', self._cfgs, self._nrs.ctypes.data,
+                len(self.plan['cfgs']), self.N, _lib.ptr(self.agents_d), _lib.ptr(self.agent_cfg_d),
+                _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy),
+                _lib.ptr(self.map_off_d), _lib.ptr(self.overhead), _lib.ptr(out), _lib.ptr(self.out_off_d),
+                _lib.stream_handle(s)))
+        else:
+            _lib.check(_lib.call(self.context, 'get_state_mixed_as', self._cfgs, self._nrs.ctypes.data,
+                len(self.plan['cfgs']), self.N, _lib.ptr(self.agents_d), _lib.ptr(self.agent_cfg_d),
+                _lib.ptr(self.envs_d), _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy),
+                _lib.ptr(self.map_off_d), _lib.ptr(self.overhead), _lib.ptr(out), _lib.ptr(self.out_off_d), dtype_id,
+                _lib.stream_handle(s)))
         hold(s, cur, out, self.agents_d, self.agent_cfg_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy,
              self.map_off_d, self.overhead, self.out_off_d)
         return out
@@ -1071,7 +1159,7 @@ class MixedStateBatch(_ArrayUpload):
                 dst[idx] = flat
 
     def states(self, out):
-        """Per-agent views of a rendered flat tensor, in agent order."""
+        """Per-agent views of a rendered flat tensor, in agent order and in the tensor's dtype."""
         L = K.LOCAL_MAP_PIXEL_WIDTH
         views = []
         for n in range(self.N):

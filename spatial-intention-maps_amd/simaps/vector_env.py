@@ -45,8 +45,9 @@ class VectorEnvObservations:
         """reuse_outputs=R > 0: all-robots get_state() renders into a ring of R preallocated output
         batches and returns a structure of views built once per ring slot (no per-call allocation
         or per-robot view creation: ~0.2 ms of host time per 256 stacks).  The states of a call are
-        then overwritten R calls later -- copy what must live longer (the reference returns fresh
-        arrays; the default R = 0 keeps that).  With numpy=True the ring slots also hold a pinned
+        then overwritten R calls later -- what must live longer (a replay buffer's states) is better
+        rendered straight into its own store with get_state_into() than copied out of the ring (the
+        reference returns fresh arrays; the default R = 0 keeps that).  With numpy=True the ring slots also hold a pinned
         host copy: one asynchronous device->host copy per call into page-locked memory, returned as
         NumPy views (a fresh pageable copy per call otherwise).
         context: a simaps.context.Context that every launch and fault check of this object goes
@@ -168,6 +169,30 @@ class VectorEnvObservations:
                         for g in self.groups[e]])
         return res
 
+    def get_state_into(self, store, dest, stream=None):
+        """Render states straight into rows of the caller's `store` (a replay buffer's tensor, say)
+        instead of returning them: one launch over all agents of the batch
+        (StateBatch.render_into, simaps_get_state_into), no copy pass afterwards.  Returns `store`.
+
+        store: contiguous, on the batch's device, shape (capacity,) + batch.out_shape()[1:] (the
+        batch's layout; batch.alloc_store()), float32 / bfloat16 / float16 -- its dtype need not be
+        this object's `dtype`.
+        dest: an int64 device tensor with one row of the store per map slot (self.slot[(env, robot)]
+        order), -1 for a robot that is not to be rendered -- never read on the host, so which robots
+        act may be decided on the device and the call captured in a graph; or [env][robot] ints with
+        None for "not this robot" (checked for range and duplicates: ValueError)."""
+        if not isinstance(dest, torch.Tensor):
+            if len(dest) != self.num_envs or any(len(d) != len(s['robots']) for d, s in zip(dest, self.batch.scenes)):
+                raise ValueError('dest must be [env][robot] rows (None: not this robot), or a device tensor')
+            flat = [-1] * self.batch.N
+            for e, row in enumerate(dest):
+                for a, d in enumerate(row):
+                    if d is not None:
+                        if int(d) < 0:
+                            raise ValueError('dest[%d][%d] = %d: a row of the store, or None' % (e, a, d))
+                        flat[self.slot[(e, a)]] = int(d)
+            dest = flat
+        return self.batch.render_into(store, dest, stream=stream)
 
     def _get_state_with_figures(self, all_robots, awaiting, numpy, stream, figures_dir, occupancy_maps):
         import os

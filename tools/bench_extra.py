@@ -13,6 +13,9 @@
   state16        (--state16) the state stack rendered directly as bf16 / fp16 (simaps_get_state_as)
                  against the float32 render and the float32 render + cast pass: device time per
                  256 stacks, the four alternating in one process
+  store          (--store) states rendered straight into a bf16 store of 4,096 stacks at rows chosen
+                 by a device-side dest (simaps_get_state_into) against today's route, the render into
+                 a ring batch + index_copy_ into the store: all 256 agents, and a 64-agent subset
   gridgraph_large (--gridgraph-large) GridGraph on a 500 x 500 grid (beyond the LDS window: the
                  global-memory kernels of csrc/grid_large.h): images and paths, 1 and 64 per call
 
@@ -416,6 +419,98 @@ def bench_state16(args):
         f.write(''.join(json.dumps(x) + '\n' for x in lines))
 
 
+def bench_store(args):
+    """A bf16 store of `capacity` stacks filled from the render of `envs` envs of `config` (256 agents),
+    CHW: (a) render(out=ring) of all agents + store.index_copy_(0, dest, ring), today's route;
+    (b) render_into(store, dest) of the same agents; (c) a host-chosen subset of a quarter of the agents
+    rendered with slots= + the index_copy_; (d) render_into over all agents with the other three
+    quarters' destinations at -1.  The method is bench_state16's: device time by HIP events around
+    `reps` calls queued behind a blocking kernel, the variants alternating round by round in this
+    process, each reporting its rounds' median, min and max.  No ratio is fixed in advance: (b) is
+    compared with (a)'s min..max and (d) with (c)'s."""
+    scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
+    b = batch.StateBatch(scenes, layout='chw')
+    dt = torch.bfloat16
+    store = b.alloc_store(args.capacity, dtype=dt).zero_()
+    check = torch.zeros_like(store)
+    ring = b.alloc_state(dtype=dt)
+    rs = np.random.RandomState(7)
+    rows = rs.permutation(args.capacity)[:b.N].astype(np.int64)
+    dest = torch.from_numpy(rows).to(b.device)
+    sub = [int(k) for k in np.sort(rs.permutation(b.N)[:b.N // 4])]
+    ring_sub = b.alloc_state(len(sub), dtype=dt)
+    dest_sub = dest[torch.as_tensor(sub, device=b.device)].contiguous()
+    masked = np.full(b.N, -1, dtype=np.int64)
+    masked[sub] = rows[sub]
+    dest_masked = torch.from_numpy(masked).to(b.device)
+
+    def all_copy(st=store):
+        b.render(out=ring)
+        st.index_copy_(0, dest, ring)
+
+    def sub_copy(st=store):
+        b.render(out=ring_sub, slots=sub)
+        st.index_copy_(0, dest_sub, ring_sub)
+    variants = {'a_render_plus_index_copy': all_copy, 'b_render_into': lambda: b.render_into(store, dest),
+                'c_subset_render_plus_index_copy': sub_copy,
+                'd_render_into_masked': lambda: b.render_into(store, dest_masked)}
+    # the routes agree before they are timed
+    all_copy(check)
+    b.render_into(store, dest)
+    torch.cuda.synchronize()
+    assert torch.equal(store.view(torch.int16), check.view(torch.int16))
+    store.zero_()
+    check.zero_()
+    sub_copy(check)
+    b.render_into(store, dest_masked)
+    torch.cuda.synchronize()
+    assert torch.equal(store.view(torch.int16), check.view(torch.int16))
+    del check
+    for f in variants.values():
+        for _ in range(20):
+            f()
+    torch.cuda.synchronize()
+    big = torch.randn(8192, 8192, device='cuda')
+    s = torch.cuda.current_stream()
+    us = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for name, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.mm(big, big)
+            torch.mm(big, big)
+            e0.record(s)
+            for _ in range(args.reps):
+                f()
+            e1.record(s)
+            torch.cuda.synchronize()
+            us[name].append(e0.elapsed_time(e1) / args.reps * 1e3)
+    from simaps import _lib
+    _lib.check_faults()
+    lines = []
+    against = {'b_render_into': 'a_render_plus_index_copy', 'd_render_into_masked': 'c_subset_render_plus_index_copy'}
+    for name, v in us.items():
+        n = b.N if name[0] in 'ab' else len(sub)
+        line = {'row': 'store', 'variant': name, 'config': args.config, 'agents_launched': b.N if name[0] != 'c' else n,
+                'stacks_stored': n, 'channels': b.C, 'layout': 'chw', 'store_dtype': 'bfloat16',
+                'store_capacity': args.capacity, 'median_us': float(np.median(v)), 'min_us': min(v), 'max_us': max(v),
+                'rounds_us': [round(x, 3) for x in v], 'reps_per_round': args.reps}
+        if name in against:
+            o = us[against[name]]
+            line['against'] = against[name]
+            line['against_spread_us'] = [min(o), max(o)]
+            line['median_below_against_spread'] = bool(np.median(v) < min(o))
+            line['gain_us'] = float(np.median(o) - np.median(v))
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    lines.append({'row': 'store_note', 'note': 'device time per call: HIP events around reps_per_round calls queued '
+                  'behind two 8192^3 float32 matmuls, after 20 warm-up calls per variant; the variants alternate round '
+                  'by round in one process; a / c = render into a preallocated bf16 batch + store.index_copy_(0, dest, '
+                  'batch); b / d = one simaps_get_state_into launch; the destination rows are a fixed random choice '
+                  'among the store\'s rows'})
+    with open(args.out, 'w') as f:
+        f.write(''.join(json.dumps(x) + '\n' for x in lines))
+
+
 def bench_remap(args):
     """The periodic re-map of one moving robot (RobotController.step -> update_map every 200
     simulation steps, envs.py:1401-1403): a single-frame simaps_ingest, end to end (host prep +
@@ -601,6 +696,17 @@ if __name__ == '__main__':
         ap.add_argument('--reps', type=int, default=100)
         ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'state16_bench.jsonl'))
         bench_state16(ap.parse_args())
+        sys.exit(0)
+    if '--store' in sys.argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument('--store', action='store_true')
+        ap.add_argument('--config', default='lifting_4-small_divider')
+        ap.add_argument('--envs', type=int, default=64)
+        ap.add_argument('--capacity', type=int, default=4096)
+        ap.add_argument('--rounds', type=int, default=15)
+        ap.add_argument('--reps', type=int, default=100)
+        ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'store_bench.jsonl'))
+        bench_store(ap.parse_args())
         sys.exit(0)
     if '--action' in sys.argv:
         bench_action(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, awaiting=(64, 256)))
