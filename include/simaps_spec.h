@@ -1,0 +1,45 @@
+/* simaps_spec.h -- which get_state kernel a call takes.
+ *
+ * simaps_get_state's kernel reads the configuration's feature flags and layout at run time.  For the
+ * standard stacks libsimaps.so also carries instances of the same kernel body compiled with those
+ * fields fixed: simaps_get_state and simaps_ctx_get_state launch the instance
+ * whose fixed fields match the call's simaps_config, by truthiness as the device code tests them,
+ * when the call asks for no simaps_debug output (dbg NULL, or every pointer of it NULL, rec_cache
+ * included); any other call takes the generic kernel.  Room rect, H / W, line thickness, encodings,
+ * scales and rotate_rounding are never fixed.  Results, faults and errors are those of the generic
+ * kernel bit for bit; only the launch time differs.
+ *
+ * simaps_get_state_as (16-bit stacks), simaps_get_state_into and the mixed launches always take
+ * their own generic kernels.
+ *
+ * The query below is host-only: it launches nothing and needs no GPU.
+ */
+#ifndef SIMAPS_SPEC_H
+#define SIMAPS_SPEC_H
+
+#include "simaps.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SIMAPS_SPEC_ABI_VERSION 1
+
+/* instance ids */
+#define SIMAPS_SPEC_GENERIC 0 /* the generic kernel */
+#define SIMAPS_SPEC_S1 1      /* robot map, both shortest-path maps, intention map; no history map, no
+                                 intention channels, no distance-to-receptacle map; CHW */
+#define SIMAPS_SPEC_S2 2      /* S1 without the shortest-path-to-receptacle map */
+#define SIMAPS_SPEC_COUNT 3
+
+int simaps_spec_abi_version(void);
+
+/* The id of the kernel a float32 simaps_get_state call with this configuration would launch;
+ * has_debug != 0 says that the call passes a simaps_debug with some pointer set.  SIMAPS_EINVAL for a
+ * NULL cfg.  The configuration is not validated otherwise (simaps_get_state does that). */
+int simaps_get_state_instance(const simaps_config *cfg, int has_debug);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SIMAPS_SPEC_H */

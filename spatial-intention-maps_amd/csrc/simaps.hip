@@ -49,6 +49,7 @@
 #include "simaps_action.h"  // (includes simaps_ctx.h, which includes simaps.h)
 #include "simaps_state16.h"
 #include "simaps_store.h"
+#include "spec.h"
 #include "state16.h"
 #include "store.h"
 
@@ -1454,6 +1455,43 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
     g.sync();
 }
 
+#ifdef GS_SPEC_FUSED_SNAP  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
+// snap_sources + sssp_init_sources with one group barrier instead of two where every query pixel is
+// free (the common case): a free query pixel is its own snapped source, so each thread that needs a
+// source's cell tests the pixel itself and writes the source's distance 0 / its dirty line at once.
+// A pixel that is not free takes snap_sources' EDT path and sssp_init_sources as they are.
+__device__ __forceinline__ void snap_init_sources(Shared &sh, SsspScratch &S, float *dist, int nsrc, const Group &g)
+{
+    const int t = g.t, h = sh.h, w = sh.w, i0 = sh.i0, j0 = sh.j0, pw = sssp_pitch(w);
+    auto free_q = [&](int s) {
+        const int qr = sh.src_q[s][0] - i0, qc = sh.src_q[s][1] - j0;
+        return qr >= 0 && qr < h && qc >= 0 && qc < w && b_test(S.freeb[qr], qc);
+    };
+    if (t < nsrc) {
+        const bool fr = free_q(t);
+        sh.src_ok[t] = fr;
+        if (fr) {
+            sh.src_s[t][0] = sh.src_q[t][0];
+            sh.src_s[t][1] = sh.src_q[t][1];
+            dist[t * DIST_FLOATS + (sh.src_q[t][0] - i0 + 1) * pw + (sh.src_q[t][1] - j0 + 1)] = 0.0f;
+        }
+    }
+    if (t < 6) (&sh.changed[0][0])[t] = 0;
+    if (t == 6) sh.rounds = 0;
+    if (t >= 64 && t < 64 + 16) {
+        const int q = t - 64, s = q >> 3, d2 = (q >> 1) & 3, word = q & 1;
+        const int bit = s < nsrc && free_q(s) ? (d2 < 2 ? sh.src_q[s][0] - i0 : sh.src_q[s][1] - j0) : -1;
+        sh.dirty[s][d2][word] = bit >= 0 && (bit >> 6) == word ? 1ull << (bit & 63) : 0ull;
+    }
+    g.sync();
+    bool slow = false;
+    for (int s = 0; s < nsrc; s++) slow |= !sh.src_ok[s];
+    if (!slow) return;
+    snap_sources(sh, S, nsrc, g);
+    sssp_init_sources(sh, dist, nsrc, g);
+}
+#endif
+
 // the sweep group (waves 0 .. 4*nsrc-1): rounds of concurrent sweeps until one changes nothing
 // the sweep waves (waves 0 .. 4*nsrc-1, four per source): rounds of concurrent sweeps until one
 // changes nothing.  Each source runs its own rounds (its own 4-wave barrier and change flags): the
@@ -2128,6 +2166,16 @@ __device__ __forceinline__ void render_maps(const RenderCtx &rc, const Group &g,
         // released its scratch -- no barrier; else every render wave must be done with the code map
         if (!early_tile) g.sync();
         wait_scratch(sh);
+#ifdef GS_SPEC_RENDER_ZERO
+        // (the two-source instance's sweep track releases its scratch as it is: the tile's first
+        // SCRATCH_Q 16-byte words are zeroed here; the rest was zeroed in the params phase.  With one
+        // source the 12 render waves are the longer track and the sweep track keeps the zeroing.)
+        if (early_tile && cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map) {
+            uint4 *tz = reinterpret_cast<uint4 *>(tile);
+            for (int k = g.t; k < SCRATCH_Q; k += g.n) tz[k] = uint4{0u, 0u, 0u, 0u};
+            g.sync();
+        }
+#endif
         if (g.t == 0) STAMP_NB(62);
         raster_lines(sh, tile, cfg, rb, paths, encs[0], true, g, early_tile);
         if (g.t == 0) STAMP_NB(13);
@@ -2382,13 +2430,23 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
     if (dbg.cspace) {
         for (int k = t; k < h * w; k += g.n) dbg.cspace[(size_t)n * h * w + k] = b_test(S.freeb[k / w], k % w) ? 1 : 0;
     }
+#ifdef GS_SPEC_FUSED_SNAP
+    if (nsrc > 0) {
+        snap_init_sources(sh, S, dist, nsrc, g);
+        if (t == 0) STAMP_NB(48);
+    }
+#else
     if (nsrc > 0) {
         snap_sources(sh, S, nsrc, g);
         if (t == 0) STAMP_NB(48);
         sssp_init_sources(sh, dist, nsrc, g);
     }
+#endif
     // every read of the cspace scratch is done (snap_sources ended with a group sync): the render
     // group may now overwrite it with its raster tile -- zeroed here first when early_tile
+#ifdef GS_SPEC_RENDER_ZERO  // (simaps_spec.hip, two sources: the render waves, which have the slack, zero it: render_maps)
+    if (cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map) zero_tile = false;
+#endif
     if (zero_tile) {
         uint4 *tz = reinterpret_cast<uint4 *>(&S);
         for (int k = t; k < SCRATCH_Q; k += g.n) tz[k] = uint4{0u, 0u, 0u, 0u};  // the rest: render params
@@ -4155,6 +4213,11 @@ __global__ void __launch_bounds__(INGEST_RES_WG) ingest_resolve_kernel(
 
 namespace {
 thread_local char g_err[512] = "";
+#if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
+// Diagnostic builds only: the instance (simaps_spec.h) that the last float32 get_state launch took;
+// its translation unit holds the stamp table that simaps_debug_read_stamps then reads.
+int g_stamp_instance = SIMAPS_SPEC_GENERIC;
+#endif
 
 int fail(int code, const char *fmt, ...)
 {
@@ -4490,9 +4553,18 @@ const char *simaps_source_hash(void) { return SIMAPS_SOURCE_HASH; }
 // Diagnostic build only: copy the stamp table (uint64 [8192][NSTAMP]) to host memory.
 int simaps_debug_read_stamps(unsigned long long *host_out)
 {
+    if (g_stamp_instance != SIMAPS_SPEC_GENERIC) return simaps_spec::read_stamps(host_out);
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : SIMAPS_EHIP;
 }
 #endif
+
+int simaps_spec_abi_version(void) { return SIMAPS_SPEC_ABI_VERSION; }
+
+int simaps_get_state_instance(const simaps_config *cfg, int has_debug)
+{
+    if (!cfg) return fail(SIMAPS_EINVAL, "cfg is NULL");
+    return simaps_spec::instance_of(*cfg, has_debug != 0);
+}
 
 const char *simaps_last_error(void) { return g_err; }
 
@@ -4625,6 +4697,20 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
         if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_as launch: %s", hipGetErrorString(e));
         return 0;
     }
+#ifndef SIMAPS_VGPR_CAP
+    // a compile-time instance of the kernel where one matches the call (simaps_spec.h, simaps_spec.hip)
+    const int inst = simaps_spec::instance_of(*cfg, simaps_spec::any_debug(d));
+#if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
+    g_stamp_instance = inst;
+#endif
+    if (inst != SIMAPS_SPEC_GENERIC) {
+        simaps_spec::launch_get_state(inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
+                                      (float *)state, C, cx.fault_dev, (hipStream_t)stream);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
+        return 0;
+    }
+#endif
 #ifdef SIMAPS_VGPR_CAP
     static const hipError_t lds_ok =
         hipFuncSetAttribute((const void *)get_state_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);

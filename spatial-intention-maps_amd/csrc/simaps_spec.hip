@@ -1,0 +1,71 @@
+// Compile-time instances of get_state_kernel (include/simaps_spec.h, spec.h): the body is
+// get_state_kernel's (get_state_body.inc with GS_MIXED 0), compiled with the configuration's feature
+// flags and layout fixed and no simaps_debug output.  The kernel takes the call's simaps_config under
+// another name and gives the body a local `cfg` whose fixed fields are constants: every helper is
+// __forceinline__ and takes cfg by reference, so the constants fold through render_maps,
+// render_distance_channels, RenderCtx::put, sweep_track and the nsrc / cs_waves / nw decisions.
+// Room rect, H / W, thickness, encodings, scales and rotate_rounding stay run-time values.  Built
+// into libsimaps.so beside simaps.hip, whose device helpers it includes (SIMAPS_DEVICE_ONLY).
+//
+// With the flags fixed the render track ends about 3 us before the sweep track,
+// so the instances also move work off the sweep track that the generic kernel keeps there (each
+// -DSIMAPS_SPEC_NO_* restores the generic schedule, for A/B timings):
+//   GS_SPEC_FUSED_SNAP   one group barrier for snap + SSSP start (snap_init_sources)
+//   GS_SPEC_RENDER_ZERO  with two sources (8 sweep + 8 render waves) the render waves zero the released
+//                        cspace scratch (sweep_track, render_maps); with one source the 12 render waves
+//                        are the longer track and the sweep track keeps it
+#ifndef SIMAPS_SPEC_NO_FUSED_SNAP
+#define GS_SPEC_FUSED_SNAP
+#endif
+#ifndef SIMAPS_SPEC_NO_RENDER_ZERO
+#define GS_SPEC_RENDER_ZERO
+#endif
+#define SIMAPS_DEVICE_ONLY
+#include "simaps.hip"
+#include "spec.h"
+
+namespace {
+// REC: use_shortest_path_to_receptacle_map (S1: 1, S2: 0)
+template <int REC>
+__global__ void __launch_bounds__(NT) get_state_spec_kernel(
+    simaps_config cfg_in, Geometry geo, const simaps_agent *__restrict__ agents, const simaps_env *__restrict__ envs,
+    const simaps_robot *__restrict__ robots, const double *__restrict__ paths, const uint8_t *__restrict__ occupancy,
+    const float *__restrict__ overhead, float *__restrict__ state, int C, unsigned *fault)
+{
+    simaps_config cfg = cfg_in;
+    cfg.use_robot_map = 1;
+    cfg.use_distance_to_receptacle_map = 0;
+    cfg.use_shortest_path_to_receptacle_map = REC;
+    cfg.use_shortest_path_map = 1;
+    cfg.use_intention_map = 1;
+    cfg.use_history_map = 0;
+    cfg.use_intention_channels = 0;
+    cfg.layout_chw = 1;
+    const simaps_debug dbg = {};
+#define GS_MIXED 0
+#include "get_state_body.inc"
+#undef GS_MIXED
+}
+}  // namespace
+
+namespace simaps_spec {
+void launch_get_state(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
+                      const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                      const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
+                      hipStream_t stream)
+{
+    if (id == SIMAPS_SPEC_S1)
+        hipLaunchKernelGGL(get_state_spec_kernel<1>, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths,
+                           occupancy, overhead, state, C, fault);
+    else
+        hipLaunchKernelGGL(get_state_spec_kernel<0>, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths,
+                           occupancy, overhead, state, C, fault);
+}
+
+#if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
+int read_stamps(unsigned long long *host_out)
+{
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : SIMAPS_EHIP;
+}
+#endif
+}  // namespace simaps_spec

@@ -1,5 +1,5 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
-include/simaps_action.h, include/simaps_state16.h and include/simaps_store.h).
+include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h and include/simaps_spec.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -125,6 +125,13 @@ EXPORTED_STORE = ('simaps_store_abi_version', 'simaps_get_state_into', 'simaps_c
                   'simaps_get_state_mixed_as', 'simaps_ctx_get_state_mixed_as')
 
 
+# include/simaps_spec.h: which get_state kernel a call takes (host-only query)
+EXPORTED_SPEC = ('simaps_spec_abi_version', 'simaps_get_state_instance')
+SPEC_ABI_VERSION = 1  # SIMAPS_SPEC_ABI_VERSION
+SPEC_GENERIC, SPEC_S1, SPEC_S2 = 0, 1, 2  # SIMAPS_SPEC_*
+SPEC_NAMES = {SPEC_GENERIC: 'generic', SPEC_S1: 'S1', SPEC_S2: 'S2'}
+
+
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
            7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action',
            13: 'get_state_into'}
@@ -238,6 +245,14 @@ def _load(path=LIB_PATH):
         if vt != STORE_ABI_VERSION:
             raise ImportError('libsimaps store ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vt, STORE_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_instance'):  # (include/simaps_spec.h; absent only in an older revision's A/B build)
+        L.simaps_spec_abi_version.restype = i32
+        L.simaps_get_state_instance.argtypes = [ctypes.POINTER(Config), i32]
+        L.simaps_get_state_instance.restype = i32
+        vk = L.simaps_spec_abi_version()
+        if vk != SPEC_ABI_VERSION:
+            raise ImportError('libsimaps spec ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vk, SPEC_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

@@ -376,6 +376,15 @@ class StateBatch(_ArrayUpload):
         return {'cspace': z(n, h, w, dt=torch.uint8), 'sources': z(n, 2, 4, dt=torch.int32),
                 'dist': z(n, 2, h, w, dt=torch.float32), 'status': z(n, dt=torch.int32)}
 
+    def kernel_instance(self, debug=False):
+        """SIMAPS_SPEC_* id of the kernel a float32 render() takes (include/simaps_spec.h): a
+        compile-time instance for the standard stacks, 0 = the generic kernel -- always with debug
+        outputs or an enabled receptacle cache."""
+        if isinstance(debug, dict):
+            debug = any(v is not None for v in debug.values())
+        has_dbg = bool(debug) or (self._rec is not None and bool(self.flags['use_shortest_path_to_receptacle_map']))
+        return _lib.lib.simaps_get_state_instance(self.cfg, int(has_dbg))
+
     def render(self, out=None, debug=None, stream=None, slots=None, dtype=None):
         """Launch the fused kernel: the stacks of every agent (or of map slots `slots`, in that
         order) into `out` (allocated if None).  Asynchronous on `stream` (default: the current

@@ -19,14 +19,14 @@ import os
 import statistics
 import sys
 
-KERNEL = 'get_state_kernel'
+KERNELS = ('get_state_kernel', 'get_state_spec_kernel')  # the generic kernel / its compile-time instances
 
 
 def load(d):
     per = collections.defaultdict(float)
     for f in sorted(glob.glob(os.path.join(d, 'pass*_counter_collection.csv'))):
         for r in csv.DictReader(open(f)):
-            if KERNEL in r['Kernel_Name']:
+            if any(k in r['Kernel_Name'] for k in KERNELS):
                 per[(r['Counter_Name'], os.path.basename(f), r['Dispatch_Id'])] += float(r['Counter_Value'])
     agg = collections.defaultdict(list)
     for (c, _, _), v in per.items():
