@@ -1,5 +1,6 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
-include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h and include/simaps_spec.h).
+include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h and
+include/simaps_ingest_seq.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -132,6 +133,13 @@ SPEC_GENERIC, SPEC_S1, SPEC_S2 = 0, 1, 2  # SIMAPS_SPEC_*
 SPEC_NAMES = {SPEC_GENERIC: 'generic', SPEC_S1: 'S1', SPEC_S2: 'S2'}
 
 
+# include/simaps_ingest_seq.h: several frames per map slot in one launch, applied in order (with its
+# context twin)
+EXPORTED_INGEST_SEQ = ('simaps_ingest_seq_abi_version', 'simaps_ingest_seq', 'simaps_ctx_ingest_seq')
+INGEST_SEQ_ABI_VERSION = 1  # SIMAPS_INGEST_SEQ_ABI_VERSION
+MAX_SEQ = 255  # frames of one map slot per launch: the key's 8-bit tag, 0 being "no key"
+
+
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
            7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action',
            13: 'get_state_into'}
@@ -253,6 +261,18 @@ def _load(path=LIB_PATH):
         if vk != SPEC_ABI_VERSION:
             raise ImportError('libsimaps spec ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vk, SPEC_ABI_VERSION))
+    if hasattr(L, 'simaps_ingest_seq'):  # (include/simaps_ingest_seq.h; absent only in an older revision's A/B build)
+        L.simaps_ingest_seq_abi_version.restype = i32
+        # simaps_ingest's list with seq and num_seq after seg_raw
+        ing = list(L.simaps_ingest.argtypes)
+        L.simaps_ingest_seq.argtypes = ing[:8] + [vp, i32] + ing[8:]
+        L.simaps_ingest_seq.restype = i32
+        L.simaps_ctx_ingest_seq.argtypes = [vp] + list(L.simaps_ingest_seq.argtypes)
+        L.simaps_ctx_ingest_seq.restype = i32
+        vq = L.simaps_ingest_seq_abi_version()
+        if vq != INGEST_SEQ_ABI_VERSION:
+            raise ImportError('libsimaps ingest_seq ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vq, INGEST_SEQ_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

@@ -837,26 +837,54 @@ class StateBatch(_ArrayUpload):
         (default: the synthetic scenes' ids).  The camera pose comes from the current descriptor."""
         self.launch_ingest(self.prepare_ingest(depth, seg_raw, camera, slots, seg_ids), stream)
 
-    def prepare_ingest(self, depth, seg_raw, camera='forward', slots=None, seg_ids=None):
+    def prepare_ingest(self, depth, seg_raw, camera='forward', slots=None, seg_ids=None, poses=None, ordered=False):
         """The host half of ingest(): uploads the frames and packs the camera poses / body ids once;
-        launch_ingest() replays the device half (what tools/bench_extra.py times alone)."""
-        from . import camera as cam_mod, synthetic
+        launch_ingest() replays the device half (what tools/bench_extra.py times alone).
+        ordered=True: `slots` may repeat -- the frames of one map slot apply in list order, all in one
+        launch (simaps_ingest_seq, include/simaps_ingest_seq.h; at most 255 frames per slot).
+        poses: [n, 3] (x, y, heading), each frame's own camera pose (default: the current descriptor's)."""
+        from . import camera as cam_mod
         spec = cam_mod.CAMERAS[camera]
         agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
         idx = list(range(self.N)) if slots is None else [int(k) for k in slots]
-        if len(set(idx)) != len(idx):
+        seq, num_seq = None, 1
+        if ordered:
+            seq_h, num_seq = ingest_order(idx)
+            if num_seq > _lib.MAX_SEQ:
+                raise ValueError('%d frames of one map slot in one launch (at most %d)' % (num_seq, _lib.MAX_SEQ))
+            if num_seq > 1:
+                seq = torch.from_numpy(seq_h).to(self.device)
+        elif len(set(idx)) != len(idx):
             raise ValueError('one frame per map slot and launch (slots repeat)')
         dep = torch.as_tensor(depth).to(device=self.device, dtype=torch.float32).contiguous()
         seg = torch.as_tensor(seg_raw).to(device=self.device, dtype=torch.int32).contiguous()
         want = (n, spec.height_px, spec.width_px)
         if tuple(dep.shape) != want or tuple(seg.shape) != want:
             raise ValueError('depth and seg_raw must be %s' % (want,))
-        poses = [self.pose_host[self._robot_off[e] + a] for e, a in (self.agents[k] for k in idx)]
+        if poses is None:
+            poses = [self.pose_host[self._robot_off[e] + a] for e, a in (self.agents[k] for k in idx)]
+        elif np.shape(poses) != (n, 3):
+            raise ValueError('poses must be [%d, 3]' % n)
         params = spec.params_batch(poses).reshape(n, 9)
+        cam = self.ingest_buffers(spec, n)
+        return {'n': n, 'slots': np.unique(np.asarray(idx, dtype=np.int64)), 'cam': cam, 'agents': agents_d,
+                'ids': _to_dev(self.seg_ids_host(seg_ids), self.device),
+                'params': torch.from_numpy(params).to(self.device), 'depth': dep, 'seg': seg,
+                'seq': seq, 'num_seq': num_seq}
+
+    def seg_ids_host(self, seg_ids):
+        """The per-env simaps_seg_ids table (seg_ids: per-env dict of body ids; None: the synthetic
+        scenes' ids), as a host array of _lib.SEG_IDS_DTYPE."""
+        from . import synthetic
         ids = np.zeros(len(self.scenes), dtype=_lib.SEG_IDS_DTYPE)
         for f in ('min_obstacle', 'max_obstacle', 'receptacle', 'min_cube', 'max_cube'):
             ids[f] = [seg_ids[e][f] for e in range(len(self.scenes))] if seg_ids is not None else synthetic.SEG_IDS[f]
         ids['has_receptacle'] = [sc['receptacle_position'] is not None for sc in self.scenes]
+        return ids
+
+    def ingest_buffers(self, spec, n):
+        """The key map and the chunk boxes of an ingest launch of n frames (allocated / grown on first
+        use); returns the camera's simaps_camera."""
         if getattr(self, '_keys', None) is None:  # (epoch-tagged from here on: launch_ingest)
             self._keys = torch.zeros((self.N, self.H, self.W), dtype=torch.int64, device=self.device)
             self._epoch = 0
@@ -866,10 +894,7 @@ class StateBatch(_ArrayUpload):
         nbox = n * nch * 4
         if getattr(self, '_boxes', None) is None or self._boxes.numel() < nbox:
             self._boxes = torch.empty((nbox,), dtype=torch.int32, device=self.device)
-        cam = _lib.Camera(spec.height_px, spec.width_px, spec.near, spec.far, spec.cx2, spec.cy2)
-        return {'n': n, 'slots': np.asarray(idx, dtype=np.int64), 'cam': cam, 'agents': agents_d,
-                'ids': _to_dev(ids, self.device),
-                'params': torch.from_numpy(params).to(self.device), 'depth': dep, 'seg': seg}
+        return _lib.Camera(spec.height_px, spec.width_px, spec.near, spec.far, spec.cx2, spec.cy2)
 
     def reset_ingest_keys(self, stream=None):
         """Zero the ingest key map now (on `stream`).  Call it before capturing ingest() into a CUDA
@@ -898,15 +923,18 @@ class StateBatch(_ArrayUpload):
     def launch_ingest(self, prep, stream=None):
         if prep['n'] == 0:
             return
-        self._map_ver[prep['slots']] += 1  # (the receptacle cache of these slots goes stale)
+        self._map_ver[prep['slots']] += 1  # (the receptacle cache of these slots goes stale; once per slot)
+        num_seq = prep.get('num_seq', 1)  # tags the launch takes: frames of one slot (prepare_ingest ordered=True)
         s, cur = launch_stream(self.device, stream)
         with torch.cuda.stream(s):
             capturing = torch.cuda.is_current_stream_capturing()
-        # The key map's launch epoch (include/simaps.h simaps_ingest).  Eager launches count 1..255;
-        # at the wrap the map is zeroed on the launch stream first (after the last launch that used
-        # it) and the count restarts.  A launch captured into a graph replays its epoch, so it takes
-        # the zeroing mode (epoch 0: the map is all zero before and after the launch); once one was
-        # captured, the eager launches take it too, since a replay may follow any of them.
+        # The key map's launch epoch (include/simaps.h simaps_ingest).  Eager launches count 1..255,
+        # an ordered launch taking num_seq of them (epoch .. epoch + num_seq - 1, simaps_ingest_seq);
+        # when a launch's last tag would pass 255 the map is zeroed on the launch stream first (after the
+        # last launch that used it) and the count restarts.  A launch captured into a graph replays
+        # its epoch, so it takes the zeroing mode (epoch 0: the map is all zero before and after the
+        # launch); once one was captured, the eager launches take it too, since a replay may follow
+        # any of them.
         if capturing:
             self._zero_mode = True
             self._replayed[prep['slots']] = True  # (replays change these maps with no host version bump)
@@ -917,21 +945,35 @@ class StateBatch(_ArrayUpload):
                     self._keys.zero_()
             self._epoch = epoch = 0
         else:
-            self._epoch = getattr(self, '_epoch', 0) + 1
-            if self._epoch > 255:
+            epoch = getattr(self, '_epoch', 0) + 1
+            if epoch + num_seq - 1 > 255:
                 self._wait_last_ingest(s)
                 with torch.cuda.stream(s):
                     self._keys.zero_()
-                self._epoch = 1
-            epoch = self._epoch
-        _lib.check(_lib.call(self.context, 'ingest', self.cfg, prep['cam'], prep['n'], _lib.ptr(prep['agents']),
-            _lib.ptr(prep['ids']), _lib.ptr(prep['params']), _lib.ptr(prep['depth']), _lib.ptr(prep['seg']),
-            _lib.ptr(self.overhead), _lib.ptr(self.occupancy), _lib.ptr(self._keys), _lib.ptr(self._boxes), epoch,
-            _lib.stream_handle(s)))
+                epoch = 1
+            self._epoch = epoch + num_seq - 1  # the last tag in use
+        args = [self.cfg, prep['cam'], prep['n'], _lib.ptr(prep['agents']), _lib.ptr(prep['ids']),
+                _lib.ptr(prep['params']), _lib.ptr(prep['depth']), _lib.ptr(prep['seg'])]
+        tail = [_lib.ptr(self.overhead), _lib.ptr(self.occupancy), _lib.ptr(self._keys), _lib.ptr(self._boxes), epoch,
+                _lib.stream_handle(s)]
+        if num_seq == 1:
+            _lib.check(_lib.call(self.context, 'ingest', *(args + tail)))
+        else:
+            _lib.check(_lib.call(self.context, 'ingest_seq', *(args + [_lib.ptr(prep['seq']), num_seq] + tail)))
         if not capturing:
             self._ingest_stream = s
-        hold(s, cur, prep['ids'], prep['params'], prep['depth'], prep['seg'], prep['agents'], self.overhead,
-             self.occupancy, self._keys, self._boxes)
+        hold(s, cur, prep['ids'], prep['params'], prep['depth'], prep['seg'], prep['agents'], prep.get('seq'),
+             self.overhead, self.occupancy, self._keys, self._boxes)
+
+
+def ingest_order(slots):
+    """seq [n] int32 and num_seq of an ordered ingest launch (include/simaps_ingest_seq.h): each
+    frame's position among the frames of its own map slot, in list order; 1 + the largest."""
+    seen = {}
+    seq = np.zeros(len(slots), dtype=np.int32)
+    for n, k in enumerate(slots):
+        seq[n] = seen[k] = seen.get(k, -1) + 1
+    return seq, (int(seq.max()) + 1 if len(slots) else 1)
 
 
 def _point_lists(pts, cnt, *extra):

@@ -32,6 +32,35 @@ def robot_groups(scene):
     return groups
 
 
+def _same_seg_ids(a, b):
+    return a is b or (a is not None and b is not None and list(a) == list(b))
+
+
+class _MapQueueStage:
+    """The pinned staging buffer of VectorEnvObservations.queue_map_update for one camera: `cap`
+    frames and, ahead of them, what an ordered ingest launch reads besides the frames (`meta` bytes:
+    camera poses, agent records, seq, the per-env body ids).  Layout: [meta | depth frames | seg
+    frames]; the NumPy views below write into it."""
+
+    def __init__(self, cap, spec, num_envs):
+        self.cap, self.spec = cap, spec
+        self.frame = spec.height_px * spec.width_px * 4  # bytes of one depth (float32) or seg (int32) frame
+        self.agents_off = cap * 72                       # after the [cap, 9] float64 camera poses
+        self.seq_off = self.agents_off + cap * _lib.AGENT_DTYPE.itemsize
+        self.ids_off = self.seq_off + cap * 4
+        self.meta = -(-(self.ids_off + num_envs * _lib.SEG_IDS_DTYPE.itemsize) // 256) * 256
+        self.seg_off = self.meta + cap * self.frame
+        self.host = torch.empty((self.meta + 2 * cap * self.frame,), dtype=torch.uint8).pin_memory()
+        h = self.host.numpy()
+        shape = (cap, spec.height_px, spec.width_px)
+        self.params = h[:self.agents_off].view(np.float64).reshape(cap, 9)
+        self.agents = h[self.agents_off:self.seq_off].view(_lib.AGENT_DTYPE)
+        self.seq = h[self.seq_off:self.ids_off].view(np.int32)
+        self.ids = h[self.ids_off:self.ids_off + num_envs * _lib.SEG_IDS_DTYPE.itemsize].view(_lib.SEG_IDS_DTYPE)
+        self.depth = h[self.meta:self.seg_off].view(np.float32).reshape(shape)
+        self.seg = h[self.seg_off:].view(np.int32).reshape(shape)
+
+
 class VectorEnvObservations:
     """The observation half of E VectorEnvs of one configuration, device-resident.
 
@@ -41,7 +70,8 @@ class VectorEnvObservations:
     (C, 96, 96) planes (what a conv policy consumes, policies.py:44-45) -- states returned by
     get_state() are always the reference's (96, 96, C) index order (views for 'chw')."""
 
-    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0, context=None, dtype=torch.float32):
+    def __init__(self, scenes, device='cuda', layout='hwc', reuse_outputs=0, context=None, dtype=torch.float32,
+                 map_queue=64):
         """reuse_outputs=R > 0: all-robots get_state() renders into a ring of R preallocated output
         batches and returns a structure of views built once per ring slot (no per-call allocation
         or per-robot view creation: ~0.2 ms of host time per 256 stacks).  The states of a call are
@@ -55,8 +85,18 @@ class VectorEnvObservations:
         dtype: torch.float32 (the reference's), or torch.bfloat16 / torch.float16: every state is
         rendered directly in that format (StateBatch.render(dtype=...)), the ring and the pinned host
         copies included.  numpy=True returns float16 states as np.float16; NumPy has no bfloat16, so
-        get_state(numpy=True) with torch.bfloat16 raises ValueError."""
+        get_state(numpy=True) with torch.bfloat16 raises ValueError.
+        map_queue: how many camera frames queue_map_update() holds before it flushes by itself (its
+        pinned staging buffer is allocated on first use)."""
         _lib.state_dtype_id(dtype)
+        if int(map_queue) < 1:
+            raise ValueError('map_queue must be >= 1')
+        self._mq_cap = int(map_queue)
+        self._mq_stage = {}     # camera name -> _MapQueueStage (allocated on first use)
+        self._mq_n = 0          # queued frames
+        self._mq_camera = self._mq_seg_ids = None
+        self._mq_count = {}     # map slot -> frames of it in the queue
+        self._mq_ev = None      # the last flush's upload: the staging buffer is rewritten only after it
         self.dtype = dtype
         self.batch = _batch.StateBatch(scenes, device=device, layout=layout, context=context)
         self._ring = [None] * int(reuse_outputs)
@@ -79,6 +119,7 @@ class VectorEnvObservations:
                 raise ValueError('update() keeps the batch shape: same envs, same robots per env')
             self.batch.set_descriptors(scenes)
         if occupancy is not None or overhead is not None:
+            self.flush_map_updates()  # (queued frames are older than the maps that replace them)
             self.batch.set_maps(occupancy, overhead, slots)
 
     def update_arrays(self, pose, target, idle, lifting, waypoints, wp_count, wp_index):
@@ -93,9 +134,83 @@ class VectorEnvObservations:
         the camera poses of the current descriptor.  Called for every robot by VectorEnv.reset()
         (envs.py:214-215), for the awaiting robots at the end of VectorEnv.step() (277-280), and for
         a single moving robot every 200 simulation steps by RobotController.step (1401-1403) --
-        successive calls apply in order (stream order)."""
+        successive calls apply in order (stream order), after any frames queue_map_update() holds."""
+        self.flush_map_updates(stream)
         self.batch.ingest(depth, seg_raw, camera=camera, slots=[self.slot[(e, a)] for e, a in robots],
                           seg_ids=seg_ids, stream=stream)
+
+    # -- deferred re-maps ------------------------------------------------------------------------
+    def queue_map_update(self, robots, depth, seg_raw, camera='forward', seg_ids=None):
+        """update_map() deferred: the frames of `robots` ([(env, robot), ...]; a robot may repeat, here
+        and across calls) are copied into a pinned staging buffer with each frame's camera pose, taken
+        from the descriptor as it is now, and nothing is launched.  flush_map_updates() sends all
+        queued frames to the device together and applies them in ONE ordered launch
+        (simaps_ingest_seq): every robot's maps come out as if update_map() had been called per frame
+        in queue order.  Nothing reads a robot's maps between its periodic re-maps
+        (RobotController.step, envs.py:1401-1403), so they can wait: every method that reads or
+        replaces maps (get_state, get_state_into, distance_to_receptacle, shortest_path,
+        store_new_action, update_map, update with maps) flushes first, and so do a full queue, a frame
+        of another camera or with other seg_ids, and the 256th queued frame of one robot."""
+        from . import camera as cam_mod
+        spec = cam_mod.CAMERAS[camera]
+        dep, seg = np.asarray(depth), np.asarray(seg_raw)
+        want = (len(robots), spec.height_px, spec.width_px)
+        if dep.shape != want or seg.shape != want:
+            raise ValueError('depth and seg_raw must be %s' % (want,))
+        slots = [self.slot[(int(e), int(a))] for e, a in robots]
+        b = self.batch
+        for k, slot in enumerate(slots):
+            if self._mq_n and (self._mq_n == self._mq_cap or camera != self._mq_camera or
+                               not _same_seg_ids(seg_ids, self._mq_seg_ids) or
+                               self._mq_count.get(slot, 0) == _lib.MAX_SEQ):
+                self.flush_map_updates()
+            st = self._mq_stage.get(camera)
+            if st is None:
+                st = self._mq_stage[camera] = _MapQueueStage(self._mq_cap, spec, len(b.scenes))
+            n = self._mq_n
+            if n == 0:
+                if self._mq_ev is not None:  # the last flush's copies still read the staging buffer
+                    self._mq_ev.synchronize()
+                    self._mq_ev = None
+                self._mq_camera, self._mq_seg_ids = camera, seg_ids
+                st.ids[:] = b.seg_ids_host(seg_ids)
+            e, a = b.agents[slot]
+            st.depth[n], st.seg[n] = dep[k], seg[k]
+            st.params[n] = spec.params(*b.pose_host[b._robot_off[e] + a])
+            st.agents[n] = (e, a, slot)
+            st.seq[n] = self._mq_count.get(slot, 0)
+            self._mq_count[slot] = int(st.seq[n]) + 1
+            self._mq_n = n + 1
+
+    @property
+    def pending_map_updates(self):
+        """The number of frames queue_map_update() holds."""
+        return self._mq_n
+
+    def flush_map_updates(self, stream=None):
+        """Send the queued frames to the device (the staging buffer's used part, asynchronously on
+        the current stream: one copy when the queue is full, else one for poses / order / depth and
+        one for the segmentation frames) and apply them in one ordered launch on `stream`."""
+        n = self._mq_n
+        if n == 0:
+            return
+        b, st = self.batch, self._mq_stage[self._mq_camera]
+        dev = torch.empty((st.meta + 2 * n * st.frame,), dtype=torch.uint8, device=b.device)
+        if n == st.cap:
+            dev.copy_(st.host, non_blocking=True)
+        else:
+            head = st.meta + n * st.frame
+            dev[:head].copy_(st.host[:head], non_blocking=True)
+            dev[head:].copy_(st.host[st.seg_off:st.seg_off + n * st.frame], non_blocking=True)
+        self._mq_ev = torch.cuda.Event()
+        self._mq_ev.record(torch.cuda.current_stream(b.device))
+        num_seq = max(self._mq_count.values())
+        prep = {'n': n, 'slots': np.fromiter(self._mq_count, dtype=np.int64), 'cam': b.ingest_buffers(st.spec, n),
+                'agents': dev[st.agents_off:], 'ids': dev[st.ids_off:], 'params': dev, 'depth': dev[st.meta:],
+                'seg': dev[st.meta + n * st.frame:], 'seq': dev[st.seq_off:] if num_seq > 1 else None,
+                'num_seq': num_seq}
+        self._mq_n, self._mq_count = 0, {}
+        b.launch_ingest(prep, stream)
 
     # -- VectorEnv.get_state ---------------------------------------------------------------------
     def get_state(self, all_robots=False, awaiting=None, save_figures=False, numpy=False, stream=None,
@@ -113,6 +228,7 @@ class VectorEnvObservations:
         if numpy and self.dtype == torch.bfloat16:
             raise ValueError('numpy=True with dtype=torch.bfloat16: NumPy has no bfloat16 (take device tensors, or '
                              'torch.float16 / torch.float32 states)')
+        self.flush_map_updates(stream)
         if save_figures:
             return self._get_state_with_figures(all_robots, awaiting, numpy, stream, figures_dir, occupancy_maps)
         if (all_robots or awaiting is None) and self._ring and not numpy:
@@ -192,6 +308,7 @@ class VectorEnvObservations:
                             raise ValueError('dest[%d][%d] = %d: a row of the store, or None' % (e, a, d))
                         flat[self.slot[(e, a)]] = int(d)
             dest = flat
+        self.flush_map_updates(stream)
         return self.batch.render_into(store, dest, stream=stream)
 
     def _get_state_with_figures(self, all_robots, awaiting, numpy, stream, figures_dir, occupancy_maps):
@@ -223,6 +340,7 @@ class VectorEnvObservations:
         """Mapper.distance_to_receptacle with use_shortest_path_partial_rewards (envs.py:2190-2194):
         positions [E][A][Q] (x, y[, z]) per robot (e.g. the cubes it just moved) -> [E][A] lists of
         Python floats, each robot's own map, the receptacle as the SPFA source.  One launch."""
+        self.flush_map_updates(stream)
         Qs = [len(p) for pe in positions for p in pe]
         Q = max(Qs) if Qs else 0
         n = self.batch.N
@@ -255,6 +373,7 @@ class VectorEnvObservations:
         a robot may appear in several requests."""
         if not requests:
             return []
+        self.flush_map_updates(stream)
         slots = [self.slot[(int(ea[0]), int(ea[1]))] for ea, _, _ in requests]
         src = np.array([[float(s[0]), float(s[1])] for _, s, _ in requests], dtype=np.float64)
         tgt = np.array([[float(t[0]), float(t[1])] for _, _, t in requests], dtype=np.float64)
@@ -298,6 +417,7 @@ class VectorEnvObservations:
         res = [[[None] * len(m) for m in self.groups[e]] for e in range(self.num_envs)]
         if not order:
             return res
+        self.flush_map_updates(stream)
         q = None
         if rows:
             q = []
