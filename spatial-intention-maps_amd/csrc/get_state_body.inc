@@ -38,6 +38,18 @@
                             tail_cells_off(cfg.room_h, cfg.room_w) + LW * LW * 2 <= DIST_FLOATS * 4;
     if (tid < 16) (&sh.bar[0][0])[tid] = 0u;
     if (tid == 16) sh.scratch_free = cs_waves == 0;
+#if defined(GS_SPEC_EARLY_OCC) && !GS_MIXED
+    // (simaps_spec.hip: the sweep waves' occupancy loads need the agent record only, so they are
+    // issued here, ahead of the env record and the entry barrier, and handed to sweep_track)
+    OccLoad4<512> pre8;
+    OccLoad4<256> pre4;
+    const bool pre_occ = (tid >> 6) < cs_waves && nsrc > 0 && occ4_ok(H, W, cfg.room_j0);
+    if (pre_occ) {
+        const uint8_t *occ_slot = occupancy + (size_t)ag.map_slot * H * W;
+        if (cs_waves == 8) cspace_load4<512>(pre8, occ_slot, H, W, cfg.room_i0, cfg.room_j0, cfg.room_h, tid);
+        else cspace_load4<256>(pre4, occ_slot, H, W, cfg.room_i0, cfg.room_j0, cfg.room_h, tid);
+    }
+#endif
     simaps_env ev = envs[ag.env];
     // descriptors come through the C ABI unchecked: clamp what would index past the LDS tables
     // (robot records, segment slots) and report it (SIMAPS_FAULT_DESCRIPTOR)
@@ -77,6 +89,11 @@
         const uint8_t *occ_base = occupancy + ((int64_t)map_off[ag.map_slot] - (int64_t)ag.map_slot * H * W);
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
+#elif defined(GS_SPEC_EARLY_OCC)  // (a sweep wave: pre_occ is sweep_track's own use4, so the loads are there when it wants them)
+        if (cs_waves == 8)
+            sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile, &pre8);
+        else
+            sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile, &pre4);
 #else
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
@@ -194,6 +211,15 @@
                 }
             }
         }
+#if defined(GS_SPEC_EARLY_ZERO) && defined(GS_SPEC_RENDER_ZERO)
+        // (simaps_spec.hip, two sources: the sweep track has usually released its scratch by now, so
+        // each render wave zeroes its share of the tile's first SCRATCH_Q words ahead of the barrier
+        // below, which the stamps need anyway, and the first raster pass starts without one of its
+        // own; a wave that finds the scratch still held raises the late flag bar[1][3] instead and
+        // render_maps zeroes after its wait, as before)
+        if (early_tile && cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map)
+            zero_scratch_early(sh, tile, g);
+#endif
         g.sync();
         if (t == 0) STAMP_NB(1);
 #if GS_MIXED

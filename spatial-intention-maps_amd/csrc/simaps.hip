@@ -1222,7 +1222,8 @@ constexpr bool SSSP_CHECK = false;  // the product: inline marks + a confirming 
 // next part relaxes out of -- marked dirty for it when this part improved that line.
 constexpr bool SSSP_INLINE_MARKS = !SSSP_CHECK;
 __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_in, uint64_t (*dm)[2], int &steps,
-                                      int part = 0, int nparts = 1, bool marks = SSSP_INLINE_MARKS)
+                                      int part = 0, int nparts = 1, bool marks = SSSP_INLINE_MARKS,
+                                      unsigned long long *clk = nullptr)  // (stamp build: clocks around the asm loop)
 {
     lds_float *D = (lds_float *)Dg;  // the distance arrays live in LDS: keep ds_* addressing
     // wave-uniform loop bounds: scalar loop control, no exec-mask merges at the back edge
@@ -1262,6 +1263,7 @@ __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_i
     if (pw == 95
     ) {  // every BASELINE room is 92 columns wide (pitch 95): the asm loop with immediate offsets
         SweepOut o;
+        if (clk) clk[0] = __builtin_amdgcn_s_memtime();
         switch (dir) {
         case 0: o = sweep_asm<0, 2, 95>(D, h, w, t0, tmax, t1); break;
         case 1: o = sweep_asm<1, 2, 95>(D, h, w, t0, tmax, t1); break;
@@ -1269,6 +1271,33 @@ __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_i
         default: o = h <= 63 ? sweep_asm<3, 1, 95>(D, w, h, t0, tmax, t1) : sweep_asm<3, 2, 95>(D, w, h, t0, tmax, t1); break;
         }
         steps += o.steps;
+        if (clk) clk[1] = __builtin_amdgcn_s_memtime();
+#ifdef GS_SPEC_FLAT_MARKS  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
+        // The same marks as below without the lane-0 diamonds: the operands are wave-uniform and
+        // zero where nothing improved (an OR with 0 changes nothing), and six lanes issue the six
+        // non-returning 64-bit ORs as one LDS instruction.  They still follow the sweep's writes in the wave's
+        // LDS order (its asm drained them) and precede the wave's arrival at the round's barrier, so
+        // a decrease is either seen by a later snapshot's sweep or left marked.
+        if (marks && nparts == 1) {
+            const bool any = o.lanes != 0;
+            const int a = max(fwd ? o.imin : len - 1 - o.imax, 0), b = min(fwd ? o.imax : len - 1 - o.imin, 127);
+            const bool rng = any && a <= b;
+            const uint64_t rlo = rng && a <= 63 ? bits64(a, min(b, 63)) : 0ull;
+            const uint64_t rhi = rng && b >= 64 ? bits64(max(a, 64) - 64, b - 64) : 0ull;
+            const bool one = span <= 63;
+            const uint64_t lo = one ? o.lanes : spread2((uint32_t)o.lanes);
+            const uint64_t hi = one ? 0ull : spread2((uint32_t)(o.lanes >> 32));
+            // one LDS instruction: lanes 0 / 1 the opposite direction's two words, lanes 2 .. 5 the
+            // words of the two perpendicular directions (dm[p], dm[p + 1]: four consecutive words)
+            const int p = vert ? 2 : 0;
+            if (lane < 6) {
+                uint64_t *dst = &dm[0][0] + (lane < 2 ? 2 * (dir ^ 1) + lane : 2 * p + lane - 2);
+                const uint64_t val = lane < 2 ? (lane ? rhi : rlo) : (lane & 1 ? hi : lo);
+                __hip_atomic_fetch_or(dst, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            return any;
+        }
+#endif
         if (!o.lanes) return false;
         if (marks && lane == 0) {
             const int a = fwd ? o.imin : len - 1 - o.imax, b = fwd ? o.imax : len - 1 - o.imin;
@@ -1456,6 +1485,119 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
     g.sync();
 }
 
+#ifdef SIMAPS_PHASE_STAMPS
+// Stamp 79 (stamp build only): the round boundary of source 0 between rounds 1 and 2, in shader
+// clocks: from the end of a wave's sweep loop in round 1 (before its marks) to the start of its
+// sweep loop in round 2 (after its snapshot).  Every wave of the source measures its own; the
+// smallest is the last arriver's, which waited for nobody.  Kept as a maximum of the complement in
+// the source's unused barrier word bar[2][3] and written out by ROUND_BOUNDARY_FLUSH after the rounds.
+#define ROUND_BOUNDARY_STAMP(sh, s, round, bclk, bend)                                                       \
+    do {                                                                                                    \
+        if ((s) == 0 && (round) == 2 && (bend) && (bclk)[0] && (threadIdx.x & 63) == 0)                     \
+            __hip_atomic_fetch_max(&(sh).bar[2][3], 0x7fffffffu - (unsigned)((bclk)[0] - (bend)), __ATOMIC_RELAXED, \
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);                                           \
+        (bend) = (bclk)[1];                                                                                 \
+    } while (0)
+#define ROUND_BOUNDARY_FLUSH(sh)                                                         \
+    do {                                                                                 \
+        if (threadIdx.x == 0 && (sh).bar[2][3] && blockIdx.x < MAX_STAMP_WG)             \
+            g_stamps[blockIdx.x * NSTAMP + 79] = 0x7fffffffu - (sh).bar[2][3];           \
+    } while (0)
+#endif
+
+#ifdef GS_SPEC_ROUND_WORD  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
+// sssp_rounds with one LDS word per source and round instead of a change flag plus a group barrier.
+// The storage of sh.changed[s][3] serves as three rotating 32-bit round words.  A wave arrives at
+// round r with one returning add of 1 + (improved << 8) to word r % 3: the value it gets back plus
+// its own addend tells the last arriver (low byte 4) both that the round is complete and whether any
+// wave improved a cell (the bits above), with no generation word, no counter reset and no second
+// read.  The others poll the same word (relaxed loads, s_sleep, the bounded spin with the timeout
+// flag in bar[2 + s][2]) until its low byte is 4 and take the change bits from the value they hold:
+// every arrival has been added by then, so every wave reads the same bits.
+// The word of round r + 1 is zeroed by the source's first wave at the start of round r, where
+// changed[(round + 1) % 3] was zeroed.  Ordering: (a) that wave's own arrival in round r follows the
+// store in its LDS order, and nobody arrives at word r + 1 before round r is complete, which needs
+// that arrival -- so the zero precedes every add to the word; (b) the word's previous use was round
+// r - 2: each wave's last read of it precedes its own arrival at round r - 1, and the zeroing wave
+// has seen round r - 1 complete, so nobody reads it any more.  (The three words start at zero:
+// snap_init_sources / sssp_init_sources, before the group barrier.)
+// The fences stay local-only around relaxed atomics (an acquire / release atomic would add vmcnt(0)).
+// h / w / pitch / direction and the source's src_ok are made uniform once, not per round.
+__device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
+{
+    static_assert(!SSSP_CHECK, "the fixpoint-check build keeps sssp_rounds (simaps_spec.hip)");
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = __builtin_amdgcn_readfirstlane(sh.h), w = __builtin_amdgcn_readfirstlane(sh.w);
+    const int pw = sssp_pitch(w);
+    const int max_rounds = h * w + 16;  // a converged round changes nothing; the cap guards a bug
+    const int s = wave >> 2;
+    const int dir = (wave + 2 * s) & 3;
+    const bool ok = __builtin_amdgcn_readfirstlane(sh.src_ok[s]) != 0;
+    unsigned *word = reinterpret_cast<unsigned *>(sh.changed[s]);
+    unsigned *tmo = &sh.bar[2 + s][2];
+    float *D = dist + s * DIST_FLOATS;
+    if ((dir >= 2) == (w >= h)) __builtin_amdgcn_s_setprio(3);  // (as sssp_rounds: the longer sweeps first)
+    else __builtin_amdgcn_s_setprio(2);
+    int steps = 0;
+#ifdef SIMAPS_PHASE_STAMPS
+    unsigned long long bend = 0;
+#endif
+    for (int round = 0;; round++) {
+        if ((tid & 255) == 0) __hip_atomic_store(&word[(round + 1) % 3], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef SIMAPS_PHASE_STAMPS
+        if (tid == 0 && round < 4) STAMP_NB(18 + round);
+        if (round == 0) STAMP_NB(32 + wave);
+        if (round == 0 && wave == 0) STAMP_CLK(44);
+        unsigned long long bclk[2] = {0, 0};
+        const bool imp = ok && sweep(D, h, w, pw, dir, sh.dirty[s], steps, 0, 1, SSSP_INLINE_MARKS, bclk);
+        ROUND_BOUNDARY_STAMP(sh, s, round, bclk, bend);
+        if (round == 0 && wave == 0) STAMP_NB(22);
+        if (round == 0 && wave == 2) STAMP_NB(23);
+        if (round == 0) STAMP_NB(24 + wave);
+        if (round == 0 && wave == 0) STAMP_CLK(45);
+#else
+        const bool imp = ok && sweep(D, h, w, pw, dir, sh.dirty[s], steps);
+#endif
+        unsigned v = 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        if ((tid & 63) == 0) {
+            unsigned *wr = &word[round % 3];
+            const unsigned add = 1u + (imp ? 1u << 8 : 0u);
+            // (the instruction itself: the compiler's atomic optimizer would wrap a one-lane
+            // fetch_add in a lane scan)
+            const uint32_t wa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned *)wr;
+            asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(wa), "v"(add) : "memory");
+            v += add;
+            unsigned spins = 0;
+            while ((v & 0xffu) != 4u) {
+                __builtin_amdgcn_s_sleep(1);
+#ifdef SIMAPS_DIAG_FLAG_TIMEOUT  // (as Group::sync: flag at the real site on the first spin, keep waiting)
+                if (spins == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
+                if (++spins > (1u << 22)) {  // ~0.1 s: never in a correct run (SIMAPS_FAULT_TIMEOUT);
+                    // the wave leaves the rounds (no change bits), so the others wait at most once more
+                    __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    v = 0;
+                    break;
+                }
+                v = __hip_atomic_load(wr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        v = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+        if (!(v >> 8) || round >= max_rounds) {
+            if ((tid & 255) == 0)  // cap hit: 1 << 20 (status bit 1)
+                __hip_atomic_fetch_max(&sh.rounds, round >= max_rounds ? 1 << 20 : round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef SIMAPS_PHASE_STAMPS
+            if ((tid & 63) == 0 && blockIdx.x < MAX_STAMP_WG) g_stamps[blockIdx.x * NSTAMP + 64 + wave] = steps;
+            if (s == 0) ROUND_BOUNDARY_FLUSH(sh);
+#endif
+            break;
+        }
+    }
+}
+#endif
+
 #ifdef GS_SPEC_FUSED_SNAP  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
 // snap_sources + sssp_init_sources with one group barrier instead of two where every query pixel is
 // free (the common case): a free query pixel is its own snapped source, so each thread that needs a
@@ -1512,18 +1654,29 @@ __device__ __forceinline__ void sssp_rounds(Shared &sh, float *dist, int nsrc, c
         else __builtin_amdgcn_s_setprio(2);
     }
     int steps = 0;  // lines this wave processed (diagnostics)
+#ifdef SIMAPS_PHASE_STAMPS
+    unsigned long long bend = 0;  // (round boundary, stamp 79: see ROUND_BOUNDARY_STAMP)
+#endif
     for (int round = 0;; round++) {
         if ((tid & 255) == 0) changed[(round + 1) % 3] = 0;
 #ifdef SIMAPS_PHASE_STAMPS
         if (tid == 0 && round < 4) STAMP_NB(18 + round);
         if (round == 0) STAMP_NB(32 + wave);
         if (round == 0 && wave == 0) STAMP_CLK(44);
+        unsigned long long bclk[2] = {0, 0};
 #endif
         // waves go to SIMD (wave % 4): source 1's directions are rotated by 2 so that every SIMD
         // hosts one row sweep and one column sweep (the long ones would otherwise share two SIMDs)
+#ifdef SIMAPS_PHASE_STAMPS
+        if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps, 0, 1,
+                                  SSSP_INLINE_MARKS, bclk) && (tid & 63) == 0 && !SSSP_CHECK)
+            changed[round % 3] = 1;
+        ROUND_BOUNDARY_STAMP(sh, s, round, bclk, bend);
+#else
         if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps) && (tid & 63) == 0 &&
             !SSSP_CHECK)
             changed[round % 3] = 1;
+#endif
 #ifdef SIMAPS_PHASE_STAMPS
         if (round == 0 && wave == 0) STAMP_NB(22);
         if (round == 0 && wave == 2) STAMP_NB(23);
@@ -1551,6 +1704,7 @@ __device__ __forceinline__ void sssp_rounds(Shared &sh, float *dist, int nsrc, c
                 __hip_atomic_fetch_max(&sh.rounds, round >= max_rounds ? 1 << 20 : round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef SIMAPS_PHASE_STAMPS
             if ((tid & 63) == 0 && blockIdx.x < MAX_STAMP_WG) g_stamps[blockIdx.x * NSTAMP + 64 + wave] = steps;
+            if (s == 0) ROUND_BOUNDARY_FLUSH(sh);
 #endif
             break;
         }
@@ -1909,6 +2063,31 @@ __device__ __forceinline__ void wait_scratch(Shared &sh)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+#ifdef GS_SPEC_EARLY_ZERO  // (simaps_spec.hip: the two-source compile-time instance of get_state_kernel only)
+// One render wave, ahead of the render group's barrier after the robot stamps: if the sweep track has
+// released its scratch (one relaxed load, the local acquire fence), zero this wave's share of the
+// tile's first SCRATCH_Q 16-byte words; otherwise raise the late flag bar[1][3] (zero since the
+// kernel's entry), which render_maps reads after that barrier: set by any wave, every wave takes
+// the wait + zero + barrier path at the raster start and zeroes all of it again (no one has
+// rasterised yet).  SIMAPS_DIAG_SCRATCH_LATE (a diagnostic build for tests/test_gpu_sweepdiet.py,
+// never the product) makes every wave take "late".
+__device__ __forceinline__ void zero_scratch_early(Shared &sh, float *tile, const Group &g)
+{
+#ifdef SIMAPS_DIAG_SCRATCH_LATE
+    const int fr = 0;
+#else
+    const int fr = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&sh.scratch_free, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+#endif
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    if (fr) {
+        uint4 *tz = reinterpret_cast<uint4 *>(tile);
+        for (int k = g.t; k < SCRATCH_Q; k += g.n) tz[k] = uint4{0u, 0u, 0u, 0u};
+    } else if ((threadIdx.x & 63) == 0) {
+        __hip_atomic_store(&sh.bar[1][3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+#endif
+
 __device__ __forceinline__ float tile_sample(const float *tile, int gi, int gj, int pi, int pj)
 {
     return tile[(gi - pi + TILE_HALF) * TILE + (gj - pj + TILE_HALF)];  // dilated at raster time (tile_put)
@@ -2166,12 +2345,21 @@ __device__ __forceinline__ void render_maps(const RenderCtx &rc, const Group &g,
         // early_tile: the code map lies outside the tile and the sweep track zeroed the tile when it
         // released its scratch -- no barrier; else every render wave must be done with the code map
         if (!early_tile) g.sync();
-        wait_scratch(sh);
+#ifdef GS_SPEC_EARLY_ZERO
+        // (zero_scratch_early: every render wave found the scratch released before the barrier after
+        // the stamps and zeroed its share there -- nothing to wait for, no zeroing, no barrier)
+        const bool zero_late = __builtin_amdgcn_readfirstlane(
+            __hip_atomic_load(&sh.bar[1][3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0;
+#else
+        const bool zero_late = true;
+#endif
+        if (zero_late || !early_tile || !(cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map))
+            wait_scratch(sh);
 #ifdef GS_SPEC_RENDER_ZERO
         // (the two-source instance's sweep track releases its scratch as it is: the tile's first
         // SCRATCH_Q 16-byte words are zeroed here; the rest was zeroed in the params phase.  With one
         // source the 12 render waves are the longer track and the sweep track keeps the zeroing.)
-        if (early_tile && cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map) {
+        if (zero_late && early_tile && cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map) {
             uint4 *tz = reinterpret_cast<uint4 *>(tile);
             for (int k = g.t; k < SCRATCH_Q; k += g.n) tz[k] = uint4{0u, 0u, 0u, 0u};
             g.sync();
@@ -2396,7 +2584,8 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
                                             const Geometry &geo, const simaps_agent &ag, const simaps_env &ev,
                                             const simaps_robot *__restrict__ robots,
                                             const uint8_t *__restrict__ occupancy, int nsrc, const simaps_debug &dbg,
-                                            int n, const Group &g, bool zero_tile)
+                                            int n, const Group &g, bool zero_tile,
+                                            const OccLoad4<G> *pre = nullptr)  // (the dword loads, already issued)
 {
     const int t = g.t, H = cfg.H, W = cfg.W;
     const int h = cfg.room_h, w = cfg.room_w;
@@ -2406,7 +2595,8 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
     if (t == 0 && ag.map_slot >= 0) STAMP_NB(43);  // the agent record has landed
 #endif
     const uint8_t *occ = occupancy + (size_t)ag.map_slot * H * W;
-    if (use4) cspace_load4<G>(occ4, occ, H, W, cfg.room_i0, cfg.room_j0, h, t);
+    if (use4 && pre) occ4 = *pre;
+    else if (use4) cspace_load4<G>(occ4, occ, H, W, cfg.room_i0, cfg.room_j0, h, t);
     const simaps_robot *rb = robots + ev.robot_off;
     if (t == 0) {
         sh.h = h;
@@ -2459,7 +2649,11 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
         STAMP_NB(3);
     }
     if (nsrc == 0) return;
+#ifdef GS_SPEC_ROUND_WORD
+    sssp_rounds_word(sh, dist);
+#else
     sssp_rounds(sh, dist, nsrc, g);
+#endif
     // the receptacle source's converged array -> its map slot's cache record (source 0 = the
     // receptacle when use_shortest_path_to_receptacle_map; envs.py:2071-2113 order)
     char *rec = dbg.rec_cache && cfg.use_shortest_path_to_receptacle_map

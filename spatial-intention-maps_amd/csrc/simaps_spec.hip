@@ -14,11 +14,35 @@
 //   GS_SPEC_RENDER_ZERO  with two sources (8 sweep + 8 render waves) the render waves zero the released
 //                        cspace scratch (sweep_track, render_maps); with one source the 12 render waves
 //                        are the longer track and the sweep track keeps it
+// and they cut serial overheads the sweep track carries beside its line steps:
+//   GS_SPEC_ROUND_WORD   one LDS word per source and round instead of a change flag plus a 4-wave
+//                        barrier (sssp_rounds_word); h / w / pitch / src_ok uniform once, not per round
+//   GS_SPEC_FLAT_MARKS   a sweep's marks as unconditional non-returning ORs of wave-uniform,
+//                        possibly-zero operands instead of lane-0 diamonds (sweep)
+//   GS_SPEC_EARLY_OCC    the sweep waves' occupancy loads issued as soon as the agent record has
+//                        landed, ahead of the env record and the entry barrier (get_state_body.inc)
+// and, on the render track, so that it does not bind in their place:
+//   GS_SPEC_EARLY_ZERO   (with GS_SPEC_RENDER_ZERO) the render waves zero the released scratch ahead
+//                        of the barrier after the robot stamps, and the first raster pass starts
+//                        without a barrier of its own (zero_scratch_early; late release: as before)
 #ifndef SIMAPS_SPEC_NO_FUSED_SNAP
 #define GS_SPEC_FUSED_SNAP
 #endif
+// (the SIMAPS_SSSP_CHECK A/B build ends its rounds with the fixpoint check, which only sssp_rounds runs)
+#if !defined(SIMAPS_SPEC_NO_ROUND_WORD) && !defined(SIMAPS_SSSP_CHECK)
+#define GS_SPEC_ROUND_WORD
+#endif
+#ifndef SIMAPS_SPEC_NO_FLAT_MARKS
+#define GS_SPEC_FLAT_MARKS
+#endif
+#ifndef SIMAPS_SPEC_NO_EARLY_OCC
+#define GS_SPEC_EARLY_OCC
+#endif
 #ifndef SIMAPS_SPEC_NO_RENDER_ZERO
 #define GS_SPEC_RENDER_ZERO
+#endif
+#if defined(GS_SPEC_RENDER_ZERO) && !defined(SIMAPS_SPEC_NO_EARLY_ZERO)
+#define GS_SPEC_EARLY_ZERO
 #endif
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"

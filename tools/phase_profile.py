@@ -70,6 +70,11 @@ def main():
            'entry_skew_us': [float(np.percentile((st[:, 77] - st[:, 77].min()) / 100.0, q)) for q in (10, 50, 90, 100)],
            'entry_to_stamp0_us': [float(np.percentile((st[:, 0] - st[:, 77]) / 100.0, q)) for q in (10, 50, 90, 100)],
            'end_after_first_entry_us': [float(np.percentile((st[:, 6] - st[:, 77].min()) / 100.0, q)) for q in (10, 50, 90, 100)],
+           # stamp 79: source 0's round boundary between rounds 1 and 2 in shader clocks, the last
+           # arriver's (ROUND_BOUNDARY_STAMP in csrc/simaps.hip); builds before it leave the slot 0
+           'round_boundary_clk': ({'median': float(np.median(st[st[:, 79] > 0, 79])), 'p10': float(np.percentile(st[st[:, 79] > 0, 79], 10)),
+                                   'p90': float(np.percentile(st[st[:, 79] > 0, 79], 90)), 'workgroups': int((st[:, 79] > 0).sum())}
+                                  if (st[:, 79] > 0).any() else None),
            'sweep_steps_per_wave': [float(np.median(st[:, 64 + w].astype(np.int64))) for w in range(8)],
            'rounds': {'median': float(np.median(st[:, 10])), 'max': int(st[:, 10].max()), 'min': int(st[:, 10].min())}}
     # SSSP edge relaxations per stack -- every cell of a swept line evaluates its 3
