@@ -833,7 +833,8 @@ class StateBatch(_ArrayUpload):
         agents if None): each robot's camera frame -- depth buffer [n, Hc, Wc] float32 and
         segmentation body ids [n, Hc, Wc] int32, as pybullet getCameraImage returns them -- becomes a
         point cloud that updates the robot's overhead and occupancy maps in place on the device.
-        camera: 'forward' (use_partial_observations) or 'overhead'; seg_ids: per-env dict of body ids
+        camera: 'forward' (use_partial_observations) or 'overhead', or a camera.CameraSpec of another
+        image size (its name picks the pose rule); seg_ids: per-env dict of body ids
         (default: the synthetic scenes' ids).  The camera pose comes from the current descriptor."""
         self.launch_ingest(self.prepare_ingest(depth, seg_raw, camera, slots, seg_ids), stream)
 
@@ -844,7 +845,7 @@ class StateBatch(_ArrayUpload):
         launch (simaps_ingest_seq, include/simaps_ingest_seq.h; at most 255 frames per slot).
         poses: [n, 3] (x, y, heading), each frame's own camera pose (default: the current descriptor's)."""
         from . import camera as cam_mod
-        spec = cam_mod.CAMERAS[camera]
+        spec = camera if isinstance(camera, cam_mod.CameraSpec) else cam_mod.CAMERAS[camera]
         agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
         idx = list(range(self.N)) if slots is None else [int(k) for k in slots]
         seq, num_seq = None, 1

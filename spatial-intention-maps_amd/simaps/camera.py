@@ -22,10 +22,12 @@ FOV = 60                     # Camera.FOV, vertical (envs.py:1880)
 
 
 class CameraSpec:
-    def __init__(self, name, aspect, near, far):
+    def __init__(self, name, aspect, near, far, height_px=None, width_px=None):
+        """height_px / width_px: another image size than the reference's (simaps_ingest takes widths
+        67 .. 1024 and frames of fewer than 2^20 pixels); the pixel scales still follow `aspect`."""
         self.name, self.aspect, self.near, self.far = name, aspect, near, far
-        self.height_px = int(1.63 * K.LOCAL_MAP_PIXEL_WIDTH)    # envs.py:1895
-        self.width_px = int(self.aspect * self.height_px)       # envs.py:1896
+        self.height_px = int(1.63 * K.LOCAL_MAP_PIXEL_WIDTH) if height_px is None else int(height_px)  # envs.py:1895
+        self.width_px = int(self.aspect * self.height_px) if width_px is None else int(width_px)      # envs.py:1896
         limit_y = math.tan(math.radians(FOV / 2))               # envs.py:1944
         limit_x = limit_y * self.aspect
         self.cx2, self.cy2 = 2 * limit_x, 2 * limit_y           # pixel_x / pixel_y scales (envs.py:1946-1947)

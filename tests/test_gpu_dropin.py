@@ -485,8 +485,9 @@ def test_ingest_reference_goldens(V):
 
 @pytest.mark.parametrize('kind', ['forward', 'overhead'])
 def test_ingest_then_get_state_vs_oracle(V, kind):
-    """update_map + get_state end to end on the device vs the oracle (fresh frames; z ties resolved
-    as 'later camera pixel wins' on both sides)."""
+    """update_map + get_state end to end on the device vs the oracle (fresh frames of
+    synthetic.camera_images, whose depth noise leaves no two points with one z: the tie rule 'later
+    camera pixel wins' is tested in tests/test_gpu_ingest_edges.py, not here)."""
     synthetic, vector_env = V
     from simaps import batch
     scenes = [synthetic.make_scene('lifting_2_throwing_2-large_empty', 210 + e) for e in range(3)]
