@@ -48,6 +48,7 @@ __device__ __forceinline__ bool act_better(float v, int i, float bv, int bi)
     return i < bi;
 }
 
+#ifndef SIMAPS_ACTION_HELPERS_ONLY  // (simaps_action_as.hip has kernels of its own)
 __global__ void __launch_bounds__(ACT_NT) action_decode_kernel(
     const simaps_agent *__restrict__ agents, const simaps_env *__restrict__ envs, const simaps_robot *__restrict__ robots,
     const float *__restrict__ q, const int64_t *__restrict__ q_off, const int32_t *__restrict__ actions_in, int flags,
@@ -107,32 +108,10 @@ __global__ void __launch_bounds__(ACT_NT) action_decode_kernel(
         }
     }
     if (tid != 0) return;
-    const simaps_robot rb = robots[r];
-    if (bad) {
-        // no action to decode: count 0, and a source and target the path launch can run on harmlessly
-        out_count[n] = 0;
-        out_source[2 * n] = out_target[2 * n] = rb.x;
-        out_source[2 * n + 1] = out_target[2 * n + 1] = rb.y;
-        post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_ACTION, n);
-        return;
-    }
-    // np.unravel_index over (K, 96, 96), then envs.py:866-869 in fp64
-    const int rem = action % ACT_PLANE, row = rem / LW, col = rem % LW;
-    const double dx = ((col + 0.5) - (double)LW / 2) / PPM, dy = ((double)LW / 2 - (row + 0.5)) / PPM;
-    const double dist = sqrt(dx * dx + dy * dy);
-    const double theta = rb.heading + atan2(-dx, dy);
-    const double tx = rb.x + dist * cos(theta), ty = rb.y + dist * sin(theta);
-    out_action[n] = action;
-    out_source[2 * n] = rb.x;
-    out_source[2 * n + 1] = rb.y;
-    out_target[2 * n] = tx;
-    out_target[2 * n + 1] = ty;
-    if (!(flags & SIMAPS_ACTION_SHORTEST_PATH)) {  // [current_position, target] (envs.py:878)
-        double *o = out_xy + (size_t)n * max_pts * 2;
-        o[0] = rb.x; o[1] = rb.y; o[2] = tx; o[3] = ty;
-        out_count[n] = 2;
-    }
+#include "action_decode_body.inc"
 }
+
+#endif
 
 // restrict_heading_range (envs.py:2567-2568): (h + pi) % (2 pi) - pi with Python's floored %
 __device__ __forceinline__ double restrict_heading(double h)
@@ -143,6 +122,7 @@ __device__ __forceinline__ double restrict_heading(double h)
     return m - PI;
 }
 
+#ifndef SIMAPS_ACTION_HELPERS_ONLY
 __global__ void __launch_bounds__(ACT_FIN_NT) action_finish_kernel(
     int N, const simaps_agent *__restrict__ agents, const simaps_env *__restrict__ envs, simaps_robot *robots,
     double *paths, const int32_t *__restrict__ actions_in, int have_q, int flags, int max_pts, ActionOffsets offsets,
@@ -159,45 +139,6 @@ __global__ void __launch_bounds__(ACT_FIN_NT) action_finish_kernel(
         out_count[n] = 0;
         return;
     }
-    const int cnt = out_count[n];
-    if (cnt < 2 || cnt > max_pts) return;  // -needed: max_points too small, nothing to finish
-    const simaps_robot rb = robots[r];
-    double *w = out_xy + (size_t)n * max_pts * 2, *hd = out_heading + (size_t)n * max_pts;
-    // waypoint headings (envs.py:881-885)
-    hd[0] = rb.heading;
-    for (int i = 1; i < cnt; i++) hd[i] = restrict_heading(atan2(w[2 * i + 1] - w[2 * i - 1], w[2 * i] - w[2 * i - 2]));
-    // the final waypoint: from the end effector's position to the robot's (envs.py:889-896)
-    const int l = cnt - 1;
-    const double ex = w[2 * l] - w[2 * l - 2], ey = w[2 * l + 1] - w[2 * l - 1];
-    const double signed_dist = sqrt(ex * ex + ey * ey) - offsets.ee[type];
-    w[2 * l] = w[2 * l - 2] + signed_dist * cos(hd[l]);
-    w[2 * l + 1] = w[2 * l - 1] + signed_dist * sin(hd[l]);
-    // avoid awkward backing up to reach the last waypoint (envs.py:899-903)
-    if (cnt > 2 && signed_dist < 0) {
-        w[2 * l - 2] = w[2 * l];
-        w[2 * l - 1] = w[2 * l + 1];
-        hd[l - 1] = restrict_heading(atan2(w[2 * l - 1] - w[2 * l - 3], w[2 * l - 2] - w[2 * l - 4]));
-    }
-    if (!(flags & SIMAPS_ACTION_WRITE_BACK)) return;
-    // The robot as the next get_state reads it, after controller.reset() (waypoint_index 1, envs.py:1386):
-    // intention path [position] + waypoints[1:-1] + [target] (envs.py:1475-1476), reversed history
-    // [position, waypoints[0]] (1478-1479, 2318), at the offsets simaps_pack_robots laid out
-    // (SIMAPS_MAX_PATH points reserved for each).
-    const double tx = out_target[2 * n], ty = out_target[2 * n + 1];
-    simaps_robot &o = robots[r];
-    o.target_x = tx;
-    o.target_y = ty;
-    o.idle = 0;
-    double *ip = paths + (size_t)2 * rb.intention_off, *hp = paths + (size_t)2 * rb.history_off;
-    for (int k = 0; k < cnt && k < SIMAPS_MAX_PATH; k++) {
-        const bool first = k == 0, last = k == cnt - 1;
-        ip[2 * k] = first ? rb.x : last ? tx : w[2 * k];
-        ip[2 * k + 1] = first ? rb.y : last ? ty : w[2 * k + 1];
-    }
-    o.intention_len = cnt;  // beyond SIMAPS_MAX_PATH: the true length, which get_state reports
-    hp[0] = rb.x;
-    hp[1] = rb.y;
-    hp[2] = w[0];
-    hp[3] = w[1];
-    o.history_len = 2;
+#include "action_finish_body.inc"
 }
+#endif

@@ -47,6 +47,7 @@
 #include "geom.h"
 #include "ingest_seq.h"
 #include "mixed.h"
+#include "action_as.h"
 #include "simaps_action.h"  // (includes simaps_ctx.h, which includes simaps.h)
 #include "simaps_state16.h"
 #include "simaps_store.h"
@@ -4838,14 +4839,13 @@ static int shortest_path_impl(simaps_ctx &cx, const simaps_config *cfg, int N, c
                                 out_count, stream);
 }
 
-// simaps_store_new_action (include/simaps_action.h): decode, path, finish on the caller's stream.  One
-// entry check for the three launches: a fault the decode kernel posts for a bad action must fail
-// the context's NEXT call, not the path launch of this one.
-static int store_new_action_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
-                                 const simaps_env *envs, simaps_robot *robots, double *paths, const uint8_t *occupancy,
-                                 const float *q, const int64_t *q_off, const int32_t *actions_in, int flags,
-                                 int max_points, int32_t *out_action, double *out_source, double *out_target,
-                                 double *out_xy, double *out_heading, int32_t *out_count, void *stream)
+// the argument checks of simaps_store_new_action, which simaps_store_new_action_as shares
+static int store_new_action_args(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                                 const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                                 const void *q, const int64_t *q_off, const int32_t *actions_in, int flags,
+                                 int max_points, const int32_t *out_action, const double *out_source,
+                                 const double *out_target, const double *out_xy, const double *out_heading,
+                                 const int32_t *out_count)
 {
     int rc = check_cfg(cfg);
     if (rc) return rc;
@@ -4857,6 +4857,22 @@ static int store_new_action_impl(simaps_ctx &cx, const simaps_config *cfg, int N
         return fail(SIMAPS_EINVAL, "NULL output");
     const bool spm = flags & SIMAPS_ACTION_SHORTEST_PATH, wb = flags & SIMAPS_ACTION_WRITE_BACK;
     if (!agents || !envs || !robots || (spm && !occupancy) || (wb && !paths)) return fail(SIMAPS_EINVAL, "NULL buffer");
+    return 0;
+}
+
+// simaps_store_new_action (include/simaps_action.h): decode, path, finish on the caller's stream.  One
+// entry check for the three launches: a fault the decode kernel posts for a bad action must fail
+// the context's NEXT call, not the path launch of this one.
+static int store_new_action_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                 const simaps_env *envs, simaps_robot *robots, double *paths, const uint8_t *occupancy,
+                                 const float *q, const int64_t *q_off, const int32_t *actions_in, int flags,
+                                 int max_points, int32_t *out_action, double *out_source, double *out_target,
+                                 double *out_xy, double *out_heading, int32_t *out_count, void *stream)
+{
+    int rc = store_new_action_args(cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in, flags, max_points,
+                                   out_action, out_source, out_target, out_xy, out_heading, out_count);
+    if (rc) return rc;
+    const bool spm = flags & SIMAPS_ACTION_SHORTEST_PATH;
     if (N == 0) return 0;
     if ((rc = pending_faults(cx))) return rc;
     const hipStream_t st = (hipStream_t)stream;
@@ -4876,6 +4892,45 @@ static int store_new_action_impl(simaps_ctx &cx, const simaps_config *cfg, int N
                        out_heading, out_count);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "store_new_action finish launch: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// simaps_store_new_action_as (include/simaps_action_as.h): the same three launches with the kernels of
+// simaps_action_as.hip around the path launch -- Q maps in q_dtype, the exploration draw -- and, with an
+// rng state, the kernel that advances it behind them.
+static int store_new_action_as_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                    const simaps_env *envs, simaps_robot *robots, double *paths,
+                                    const uint8_t *occupancy, const void *q, int q_dtype, const int64_t *q_off,
+                                    const int32_t *actions_in, const float *eps, uint64_t *rng, int flags,
+                                    int max_points, int32_t *out_action, double *out_source, double *out_target,
+                                    double *out_xy, double *out_heading, int32_t *out_count, uint8_t *out_explored,
+                                    void *stream)
+{
+    int rc = store_new_action_args(cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in, flags, max_points,
+                                   out_action, out_source, out_target, out_xy, out_heading, out_count);
+    if (rc) return rc;
+    if (q_dtype != SIMAPS_STATE_F32 && q_dtype != SIMAPS_STATE_BF16 && q_dtype != SIMAPS_STATE_F16)
+        return fail(SIMAPS_EINVAL, "q_dtype %d: SIMAPS_STATE_F32, SIMAPS_STATE_BF16 or SIMAPS_STATE_F16", q_dtype);
+    if (eps && !rng) return fail(SIMAPS_EINVAL, "eps without rng");
+    if (N == 0) return 0;
+    if ((rc = pending_faults(cx))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    simaps_action_as::launch_decode(q_dtype, N, agents, envs, robots, q, q_off, actions_in, eps, rng, flags, max_points,
+                                    out_action, out_source, out_target, out_xy, out_count, out_explored, cx.fault_dev, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SIMAPS_EHIP, "store_new_action_as decode launch: %s", hipGetErrorString(e));
+    if ((flags & SIMAPS_ACTION_SHORTEST_PATH) &&
+        (rc = shortest_path_launch(cx, cfg, N, agents, envs, robots, occupancy, out_source, out_target, max_points,
+                                   out_xy, out_count, stream)))
+        return rc;
+    const Geometry &geo = geometry();
+    double ee[4];
+    for (int t = 0; t < 4; t++)  // END_EFFECTOR_LOCATION + CUBE_WIDTH / 2 (envs.py:889)
+        ee[t] = (geo.backpack_offset + geo.base_length[t]) + geo.cube_width / 2;
+    simaps_action_as::launch_finish(N, agents, envs, robots, paths, actions_in, eps, rng, q != nullptr, flags, max_points,
+                                    ee, out_target, out_xy, out_heading, out_count, st);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(SIMAPS_EHIP, "store_new_action_as finish launch: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -5421,6 +5476,33 @@ int simaps_ctx_store_new_action(simaps_ctx *ctx, const simaps_config *cfg, int N
 {
     SIMAPS_ON_CTX(ctx, store_new_action_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in,
         flags, max_points, out_action, out_source, out_target, out_xy, out_heading, out_count, stream));
+}
+
+// include/simaps_action_as.h
+int simaps_action_as_abi_version(void) { return SIMAPS_ACTION_AS_ABI_VERSION; }
+int simaps_store_new_action_as(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                               simaps_robot *robots, double *paths, const uint8_t *occupancy, const void *q,
+                               int q_dtype, const int64_t *q_off, const int32_t *actions_in, const float *eps,
+                               uint64_t *rng, int flags, int max_points, int32_t *out_action, double *out_source,
+                               double *out_target, double *out_xy, double *out_heading, int32_t *out_count,
+                               uint8_t *out_explored, void *stream)
+{
+    simaps_ctx &cx = g_default_ctx;
+    return store_new_action_as_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, q, q_dtype, q_off, actions_in,
+                                    eps, rng, flags, max_points, out_action, out_source, out_target, out_xy,
+                                    out_heading, out_count, out_explored, stream);
+}
+int simaps_ctx_store_new_action_as(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                   const simaps_env *envs, simaps_robot *robots, double *paths,
+                                   const uint8_t *occupancy, const void *q, int q_dtype, const int64_t *q_off,
+                                   const int32_t *actions_in, const float *eps, uint64_t *rng, int flags,
+                                   int max_points, int32_t *out_action, double *out_source, double *out_target,
+                                   double *out_xy, double *out_heading, int32_t *out_count, uint8_t *out_explored,
+                                   void *stream)
+{
+    SIMAPS_ON_CTX(ctx, store_new_action_as_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, q, q_dtype, q_off,
+        actions_in, eps, rng, flags, max_points, out_action, out_source, out_target, out_xy, out_heading, out_count,
+        out_explored, stream));
 }
 
 int simaps_ingest(const simaps_config *cfg, const simaps_camera *cam, int N, const simaps_agent *agents,

@@ -1,6 +1,6 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
-include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h and
-include/simaps_ingest_seq.h).
+include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h,
+include/simaps_ingest_seq.h and include/simaps_action_as.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -140,6 +140,12 @@ INGEST_SEQ_ABI_VERSION = 1  # SIMAPS_INGEST_SEQ_ABI_VERSION
 MAX_SEQ = 255  # frames of one map slot per launch: the key's 8-bit tag, 0 being "no key"
 
 
+# include/simaps_action_as.h: the action call for 16-bit Q maps, with the exploration draw on the device
+# (with its context twin)
+EXPORTED_ACTION_AS = ('simaps_action_as_abi_version', 'simaps_store_new_action_as', 'simaps_ctx_store_new_action_as')
+ACTION_AS_ABI_VERSION = 1  # SIMAPS_ACTION_AS_ABI_VERSION
+
+
 K_NAMES = {1: 'get_state', 2: 'get_state_mixed', 3: 'sp_distance', 4: 'path', 5: 'sssp_grid', 6: 'grid_path',
            7: 'gl_sssp', 8: 'gl_tile', 9: 'gl_path', 10: 'occupancy_map', 11: 'global_maps', 12: 'action',
            13: 'get_state_into'}
@@ -273,6 +279,18 @@ def _load(path=LIB_PATH):
         if vq != INGEST_SEQ_ABI_VERSION:
             raise ImportError('libsimaps ingest_seq ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vq, INGEST_SEQ_ABI_VERSION))
+    if hasattr(L, 'simaps_store_new_action_as'):  # (include/simaps_action_as.h; absent only in an older revision's A/B build)
+        L.simaps_action_as_abi_version.restype = i32
+        # simaps_store_new_action's list with q_dtype after q, eps and rng after actions_in, out_explored before stream
+        act = list(L.simaps_store_new_action.argtypes)
+        L.simaps_store_new_action_as.argtypes = act[:8] + [i32] + act[8:10] + [vp, vp] + act[10:18] + [vp, vp]
+        L.simaps_store_new_action_as.restype = i32
+        L.simaps_ctx_store_new_action_as.argtypes = [vp] + list(L.simaps_store_new_action_as.argtypes)
+        L.simaps_ctx_store_new_action_as.restype = i32
+        vx = L.simaps_action_as_abi_version()
+        if vx != ACTION_AS_ABI_VERSION:
+            raise ImportError('libsimaps action_as ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vx, ACTION_AS_ABI_VERSION))
     v = L.simaps_abi_version()
     if v != ABI_VERSION:
         if os.environ.get('SIMAPS_AB_OLD_ABI') != str(v):

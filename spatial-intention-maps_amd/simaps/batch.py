@@ -225,15 +225,20 @@ class ActionResult:
     target [n, 2] fp64 (current position, target_end_effector_position[:2]), xy [n, max_points, 2]
     (waypoint_positions[:, :2]), heading [n, max_points] (waypoint_headings), count [n] int32
     (waypoints; -needed if max_points was too small; 0 for an agent whose action was out of range,
-    which the context's next call also reports)."""
+    which the context's next call also reports), explored [n] uint8 (1 where the action came from the
+    device's exploration draw; None for a call without exploration_eps)."""
 
-    def __init__(self, action, source, target, xy, heading, count, max_points):
+    def __init__(self, action, source, target, xy, heading, count, max_points, explored=None):
         self.action, self.source, self.target = action, source, target
         self.xy, self.heading, self.count, self.max_points = xy, heading, count, max_points
+        self.explored = explored
 
     def to_host(self):
-        """One synchronising download: dict of NumPy arrays of the same names."""
-        return {k: getattr(self, k).cpu().numpy() for k in ('action', 'source', 'target', 'xy', 'heading', 'count')}
+        """One synchronising download: dict of NumPy arrays of the same names (explored: None without
+        exploration)."""
+        out = {k: getattr(self, k).cpu().numpy() for k in ('action', 'source', 'target', 'xy', 'heading', 'count')}
+        out['explored'] = None if self.explored is None else self.explored.cpu().numpy()
+        return out
 
 
 class StateBatch(_ArrayUpload):
@@ -756,21 +761,29 @@ class StateBatch(_ArrayUpload):
         return xy, cnt
 
     def store_new_actions(self, q=None, q_off=None, actions=None, slots=None, use_shortest_path_movement=True,
-                          max_points=64, write_back=False, stream=None):
+                          max_points=64, write_back=False, stream=None, exploration_eps=None, rng=None):
         """Robot.store_new_action (envs.py:857-903) behind DQNPolicy.step's arg-max (policies.py:61-65)
         for map slots `slots` (all agents if None), in one stream-ordered device call
-        (simaps_store_new_action, include/simaps_action.h); no synchronisation, everything stays on
-        the device.  The policy outputs come as
-          q a float32 device tensor and q_off [n] int64 float offsets of each agent's [K, 96, 96] block;
+        (simaps_store_new_action, include/simaps_action.h; simaps_store_new_action_as,
+        include/simaps_action_as.h, for 16-bit outputs or device exploration); no synchronisation,
+        everything stays on the device.  The policy outputs are float32, bfloat16 or float16 (what the
+        policy emits under autocast: no cast pass) and come as
+          q a device tensor and q_off [n] int64 element offsets of each agent's [K, 96, 96] block;
           q an [n, K, 96, 96] tensor, q_off None: agent i's block is q[i] (one K for all n);
           q a list of (tensor [n_g, K_g, 96, 96], positions) pairs, one per robot group: row i of a
-            group belongs to the call's agent positions[i]; concatenated here (one copy), q_off built;
+            group belongs to the call's agent positions[i]; concatenated here in the groups' own dtype
+            (one copy; groups of different dtypes raise ValueError), q_off built;
           q None: every agent's action is given.
         actions: [n] int32 (array or device tensor), >= 0 the action index to use (the host's
         epsilon-greedy draw, policy_output.select_actions), -1 the arg-max; None: all arg-max.
         write_back=True also stores target, idle = 0 and the new intention / history paths into the
         device descriptors the next render() reads; needs the layout of set_descriptor_arrays().
-        -> ActionResult of device tensors."""
+        exploration_eps (a float, an [n] array or a float32 device tensor) with rng (a
+        policy_output.DeviceExploration, or its [2] int64 device tensor {seed, step}): the agents whose
+        action is not given explore with that probability, drawn on the device by the counter-based
+        function include/simaps_action_as.h states (not Python's `random` stream); the call advances
+        rng's step by one on the stream, so a captured call draws afresh at every replay.
+        -> ActionResult of device tensors (explored set when exploration_eps is given)."""
         agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
         if q is None and actions is None:
             raise ValueError('store_new_actions needs q, actions or both')
@@ -783,6 +796,10 @@ class StateBatch(_ArrayUpload):
         if isinstance(q, (list, tuple)):
             off = np.full(n, -1, dtype=np.int64)
             base, parts = 0, []
+            dtypes = {t.dtype for t, positions in q if t is not None and len(positions)}
+            if len(dtypes) > 1:
+                raise ValueError('the group outputs have different dtypes (%s): one dtype per call'
+                                 % ', '.join(sorted(str(d) for d in dtypes)))
             for t, positions in q:
                 if t is None or not len(positions):
                     continue
@@ -790,7 +807,7 @@ class StateBatch(_ArrayUpload):
                     raise ValueError('each group output must be [len(positions), K, 96, 96]')
                 off[np.asarray(positions, dtype=np.int64)] = base + np.arange(len(positions), dtype=np.int64) * t.shape[1] * plane
                 base += t.numel()
-                parts.append(t.to(device=self.device, dtype=torch.float32).reshape(-1))
+                parts.append(t.to(device=self.device).reshape(-1))
             if actions is None and (off < 0).any():
                 raise ValueError('agent %d has neither a policy output nor an action' % int(np.argmax(off < 0)))
             off[off < 0] = 0  # (agents with a given action: their block is not read)
@@ -802,8 +819,8 @@ class StateBatch(_ArrayUpload):
                 raise ValueError('q must be [%d, K, 96, 96] when q_off is not given' % n)
             q_off = np.arange(n, dtype=np.int64) * q.shape[1] * plane
         if q is not None:
-            if not (q.is_cuda and q.device == self.device and q.dtype == torch.float32):
-                raise ValueError('q must be a float32 tensor on %s' % self.device)
+            if not (q.is_cuda and q.device == self.device and q.dtype in _lib.STATE_DTYPES):
+                raise ValueError('q must be a float32, bfloat16 or float16 tensor on %s' % self.device)
             q = q.contiguous()
             q_off = torch.as_tensor(q_off, dtype=torch.int64).to(self.device).contiguous()
             if tuple(q_off.shape) != (n,):
@@ -815,11 +832,37 @@ class StateBatch(_ArrayUpload):
                 raise ValueError('actions must be [%d]' % n)
         i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=self.device)  # noqa: E731
         f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=self.device)  # noqa: E731
-        res = ActionResult(i32(n), f64(n, 2), f64(n, 2), f64(n, max_points, 2), f64(n, max_points), i32(n), max_points)
+        eps = None
+        if exploration_eps is not None:
+            if rng is None:
+                raise ValueError('exploration_eps needs rng (a policy_output.DeviceExploration)')
+            if np.ndim(exploration_eps) == 0 and not torch.is_tensor(exploration_eps):
+                eps = torch.full((n,), float(exploration_eps), dtype=torch.float32, device=self.device)
+            else:
+                eps = torch.as_tensor(exploration_eps, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(eps.shape) != (n,):
+                raise ValueError('exploration_eps must be a float or [%d]' % n)
+        if rng is not None:
+            rng = getattr(rng, 'tensor', rng)
+            if not (torch.is_tensor(rng) and rng.device == self.device and rng.dtype == torch.int64
+                    and tuple(rng.shape) == (2,) and rng.is_contiguous()):
+                raise ValueError('rng must be a DeviceExploration or a contiguous [2] int64 tensor on %s' % self.device)
+        res = ActionResult(i32(n), f64(n, 2), f64(n, 2), f64(n, max_points, 2), f64(n, max_points), i32(n), max_points,
+                           None if eps is None else torch.empty((n,), dtype=torch.uint8, device=self.device))
         if n == 0:
             return res
         flags = (_lib.ACTION_SHORTEST_PATH if use_shortest_path_movement else 0) | (_lib.ACTION_WRITE_BACK if write_back else 0)
         s, cur = launch_stream(self.device, stream)
+        if eps is not None or rng is not None or (q is not None and q.dtype != torch.float32):
+            _lib.check(_lib.call(self.context, 'store_new_action_as', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+                _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(q),
+                _lib.STATE_DTYPES[q.dtype] if q is not None else _lib.STATE_F32, _lib.ptr(q_off), _lib.ptr(act),
+                _lib.ptr(eps), _lib.ptr(rng), flags, max_points, _lib.ptr(res.action), _lib.ptr(res.source),
+                _lib.ptr(res.target), _lib.ptr(res.xy), _lib.ptr(res.heading), _lib.ptr(res.count),
+                _lib.ptr(res.explored), _lib.stream_handle(s)))
+            hold(s, cur, q, q_off, act, eps, rng, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy,
+                 res.action, res.source, res.target, res.xy, res.heading, res.count, res.explored)
+            return res
         _lib.check(_lib.call(self.context, 'store_new_action', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
             _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(q), _lib.ptr(q_off),
             _lib.ptr(act), flags, max_points, _lib.ptr(res.action), _lib.ptr(res.source), _lib.ptr(res.target),

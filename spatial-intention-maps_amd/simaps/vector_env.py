@@ -385,7 +385,7 @@ class VectorEnvObservations:
 
     # -- the step back from the policy ---------------------------------------------------------------
     def store_new_action(self, action=None, outputs=None, use_shortest_path_movement=True, max_points=64,
-                         write_back=False, stream=None):
+                         write_back=False, stream=None, exploration_eps=None, rng=None):
         """VectorEnv.store_new_action(action) (envs.py:224-228 -> Robot.store_new_action, 857-903) for
         every env of the batch in one device call.  action: [env][group][robot] -> action index or
         None, the structure DQNPolicy.step returns per env; outputs (optional): per env, per group
@@ -395,7 +395,12 @@ class VectorEnvObservations:
         row of `outputs` if it has one, and does not act otherwise.
         -> [env][group][robot] -> None, or a dict with the robot's new `action` ((channel, row, col)),
         `target_end_effector_position` ((x, y, 0)), `waypoint_positions` ([(x, y, 0), ...]) and
-        `waypoint_headings`, as the reference's attributes of those names read afterwards.
+        `waypoint_headings`, as the reference's attributes of those names read afterwards, and
+        `explored` (whether the action came from the device's exploration draw; False without one).
+        exploration_eps (a float) with rng (a policy_output.DeviceExploration): the robots the device
+        decides for -- those with None or -1 in `action` and a row of `outputs` -- explore with that
+        probability on the device (include/simaps_action_as.h; not Python's `random` stream, which
+        policy_output.select_actions follows).
         write_back=True: the device descriptors take the new targets and paths, so the next
         get_state() sees them without a host re-pack (needs update_arrays() descriptors)."""
         order, given, rows = [], [], {}
@@ -428,7 +433,7 @@ class VectorEnvObservations:
         slots = [self.slot[(e, a)] for e, _, _, a in order]
         r = self.batch.store_new_actions(q=q, actions=np.asarray(given, dtype=np.int32), slots=slots,
                                          use_shortest_path_movement=use_shortest_path_movement, max_points=max_points,
-                                         write_back=write_back, stream=stream)
+                                         write_back=write_back, stream=stream, exploration_eps=exploration_eps, rng=rng)
         if stream is not None:
             torch.cuda.current_stream(self.batch.device).wait_stream(stream)
         h = r.to_host()
@@ -442,7 +447,8 @@ class VectorEnvObservations:
                 'action': (a // (W * W), a % (W * W) // W, a % W),
                 'target_end_effector_position': (float(h['target'][n, 0]), float(h['target'][n, 1]), 0),
                 'waypoint_positions': [(float(x), float(y), 0) for x, y in h['xy'][n, :c]],
-                'waypoint_headings': [float(v) for v in h['heading'][n, :c]]}
+                'waypoint_headings': [float(v) for v in h['heading'][n, :c]],
+                'explored': bool(h['explored'][n]) if h['explored'] is not None else False}
         return res
 
 

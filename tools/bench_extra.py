@@ -10,6 +10,9 @@
   store_new_action (--action) the step back from the policy (simaps_store_new_action): device time
                  of the call and of its decode kernel, and the wall time per step against the same
                  result composed from torch arg-max + numpy + shortest_paths + set_descriptor_arrays
+                 then (also alone: --action-as) simaps_store_new_action_as: bf16 Q maps through it
+                 against a .float() cast + the old call, float32 through it against the old call, and
+                 the device exploration draw; rounds alternating, all recorded
   state16        (--state16) the state stack rendered directly as bf16 / fp16 (simaps_get_state_as)
                  against the float32 render and the float32 render + cast pass: device time per
                  256 stacks, the four alternating in one process
@@ -353,6 +356,81 @@ def bench_action(args):
                               'post-processing, set_descriptor_arrays' % len(tn)})
         print(json.dumps(lines[-1]), flush=True)
     out = os.path.join(ROOT, 'profiles', 'action_bench.jsonl')
+    with open(out, 'w') as f:
+        f.write(''.join(json.dumps(x) + '\n' for x in lines))
+
+
+def bench_action_as(args):
+    """simaps_store_new_action_as (include/simaps_action_as.h) against the routes it replaces, for
+    `awaiting` robots of 64 envs of lifting_4-small_divider: the call without the path launch (decode +
+    finish: the part that reads the Q maps), by bench_action's method -- HIP events around `reps` calls
+    queued behind a blocking kernel -- with the variants alternating round by round in this process.
+    Variants: f32_old (simaps_store_new_action), f32_as (the same input through the new entry point),
+    bf16_as (bf16 Q maps through the new entry point), cast_f32_old (the route bf16 outputs take
+    without it: a .float() pass, then the old call), bf16_as_eps (bf16_as with the device draw at
+    eps 0.1 and the kernel that advances the rng state).  Every round of every variant is recorded;
+    f32_as_within_f32_old says whether every f32_as round lies inside min..max of the f32_old rounds."""
+    from simaps import _lib, policy_output
+    scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
+    A = len(scenes[0]['robots'])
+    P = 2
+    lines = []
+    big = torch.randn(8192, 8192, device='cuda')
+    s = torch.cuda.current_stream()
+    for n in args.awaiting:
+        b = batch.StateBatch(scenes)
+        slots = list(range(b.N)) if n == b.N else [e * A + (e % A) for e in range(args.envs)][:n]
+        agents_d, _ = b.subset_descriptor(slots)
+        q32 = torch.randn(n, 2, 96, 96, generator=torch.Generator().manual_seed(1)).cuda().view(-1)
+        q16 = q32.to(torch.bfloat16)
+        q_off = torch.arange(n, dtype=torch.int64, device='cuda') * (2 * 9216)
+        eps = torch.full((n,), 0.1, dtype=torch.float32, device='cuda')
+        rng = policy_output.DeviceExploration(1, 'cuda')
+        i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device='cuda')  # noqa: E731
+        f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device='cuda')  # noqa: E731
+        outs = [i32(n), f64(n, 2), f64(n, 2), f64(n, P, 2), f64(n, P), i32(n)]
+        explored = torch.empty(n, dtype=torch.uint8, device='cuda')
+        head = [b.cfg, n, _lib.ptr(agents_d), _lib.ptr(b.envs_d), _lib.ptr(b.robots_d), _lib.ptr(b.paths_d),
+                _lib.ptr(b.occupancy)]
+        tail = [0, P] + [_lib.ptr(t) for t in outs]
+        sh = _lib.stream_handle(s)
+
+        def old(q):
+            _lib.check(_lib.lib.simaps_store_new_action(*(head + [_lib.ptr(q), _lib.ptr(q_off), None] + tail + [sh])))
+
+        def new(q, dt, e=None, r=None, x=None):
+            _lib.check(_lib.lib.simaps_store_new_action_as(*(head + [_lib.ptr(q), dt, _lib.ptr(q_off), None, _lib.ptr(e),
+                                                                     _lib.ptr(r)] + tail + [_lib.ptr(x), sh])))
+        variants = {'f32_old': lambda: old(q32),
+                    'f32_as': lambda: new(q32, _lib.STATE_F32),
+                    'bf16_as': lambda: new(q16, _lib.STATE_BF16),
+                    'cast_f32_old': lambda: old(q16.float()),
+                    'bf16_as_eps': lambda: new(q16, _lib.STATE_BF16, eps, rng.tensor, explored)}
+        for f in variants.values():
+            for _ in range(5):
+                f()
+        torch.cuda.synchronize()
+        runs = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for name, f in variants.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.mm(big, big)  # (the calls below queue up behind it and then run back to back)
+                e0.record(s)
+                for _ in range(args.reps):
+                    f()
+                e1.record(s)
+                torch.cuda.synchronize()
+                runs[name].append(e0.elapsed_time(e1) / args.reps * 1e3)
+        lo, hi = min(runs['f32_old']), max(runs['f32_old'])
+        lines.append({'row': 'store_new_action_as_device', 'config': args.config, 'awaiting_robots': n,
+                      'median_us': {k: float(np.median(v)) for k, v in runs.items()},
+                      'runs_us': {k: [round(x, 3) for x in v] for k, v in runs.items()},
+                      'f32_as_within_f32_old': bool(all(lo <= x <= hi for x in runs['f32_as'])),
+                      'note': 'decode + finish (no path launch, max_points 2), direct ABI calls into preallocated outputs; '
+                              'HIP events around %d calls queued behind a blocking kernel, %d rounds, the variants '
+                              'alternating round by round' % (args.reps, args.rounds)})
+        print(json.dumps(lines[-1]), flush=True)
+    out = os.path.join(ROOT, 'profiles', 'action_as_bench.jsonl')
     with open(out, 'w') as f:
         f.write(''.join(json.dumps(x) + '\n' for x in lines))
 
@@ -708,8 +786,14 @@ if __name__ == '__main__':
         ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'store_bench.jsonl'))
         bench_store(ap.parse_args())
         sys.exit(0)
+    if '--action-as' in sys.argv:  # only the rows of include/simaps_action_as.h (--action runs them too)
+        bench_action_as(argparse.Namespace(config='lifting_4-small_divider', envs=64, awaiting=(64, 256), rounds=15,
+                                           reps=100))
+        sys.exit(0)
     if '--action' in sys.argv:
         bench_action(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, awaiting=(64, 256)))
+        bench_action_as(argparse.Namespace(config='lifting_4-small_divider', envs=64, awaiting=(64, 256), rounds=15,
+                                           reps=100))
         sys.exit(0)
     if '--env-step' in sys.argv:
         bench_env_step(argparse.Namespace(config='lifting_4-small_divider', envs=64, steps=50, all=False))
