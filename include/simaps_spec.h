@@ -6,8 +6,16 @@
  * whose fixed fields match the call's simaps_config, by truthiness as the device code tests them,
  * when the call asks for no simaps_debug output (dbg NULL, or every pointer of it NULL, rec_cache
  * included); any other call takes the generic kernel.  Room rect, H / W, line thickness, encodings,
- * scales and rotate_rounding are never fixed.  Results, faults and errors are those of the generic
- * kernel bit for bit; only the launch time differs.
+ * scales and rotate_rounding do not enter this choice.  Results, faults and errors are those of the
+ * generic kernel bit for bit; only the launch time differs.
+ *
+ * Which configuration takes which kernel (the ids below; the room class: simaps_spec_room.h):
+ *   flags and layout of S1, H x W 184 x 232, room 44 x 92 (every small_* room)   S1, room class small
+ *   flags and layout of S1, any other shape (the 92 x 92 large rooms, ...)        S1
+ *   the same two rows without the shortest-path-to-receptacle map                 S2, room class small / S2
+ *   any other flags or layout, or a simaps_debug output                           generic
+ * A call of S1 / S2 whose H, W, room_h and room_w equal the small room's exactly launches that
+ * instance's twin with those four fixed as well; the id reported here stays S1 / S2.
  *
  * simaps_get_state_as (16-bit stacks), simaps_get_state_into and the mixed launches always take
  * their own generic kernels.

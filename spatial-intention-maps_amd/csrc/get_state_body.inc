@@ -89,6 +89,13 @@
         const uint8_t *occ_base = occupancy + ((int64_t)map_off[ag.map_slot] - (int64_t)ag.map_slot * H * W);
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
+#elif defined(GS_SPEC_ROOM)  // (simaps_spec.hip: GS_ROOM_H x GS_ROOM_W the instance's compile-time room, 0 in S1 / S2)
+        if (cs_waves == 8)
+            sweep_track<512, GS_ROOM_H, GS_ROOM_W>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g,
+                                                   early_tile, &pre8);
+        else
+            sweep_track<256, GS_ROOM_H, GS_ROOM_W>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g,
+                                                   early_tile, &pre4);
 #elif defined(GS_SPEC_EARLY_OCC)  // (a sweep wave: pre_occ is sweep_track's own use4, so the loads are there when it wants them)
         if (cs_waves == 8)
             sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile, &pre8);

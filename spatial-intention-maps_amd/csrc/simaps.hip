@@ -1524,15 +1524,29 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
 // snap_init_sources / sssp_init_sources, before the group barrier.)
 // The fences stay local-only around relaxed atomics (an acquire / release atomic would add vmcnt(0)).
 // h / w / pitch / direction and the source's src_ok are made uniform once, not per round.
+#ifdef GS_SPEC_ROOM
+// (the room-class instances: RH x RW the class's room and DIR the wave's direction, both compile-time,
+// so sweep()'s switch, its sweep_asm<DIR, CPL, 95> choice, len / span / fwd, the mask addresses and
+// the bits64 bounds fold; -1 / 0: the run-time values, as S1 / S2 take them)
+template <int DIR = -1, int RH = 0, int RW = 0>
+#endif
 __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
 {
     static_assert(!SSSP_CHECK, "the fixpoint-check build keeps sssp_rounds (simaps_spec.hip)");
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef GS_SPEC_ROOM
+    const int h = RH ? RH : __builtin_amdgcn_readfirstlane(sh.h), w = RW ? RW : __builtin_amdgcn_readfirstlane(sh.w);
+#else
     const int h = __builtin_amdgcn_readfirstlane(sh.h), w = __builtin_amdgcn_readfirstlane(sh.w);
+#endif
     const int pw = sssp_pitch(w);
     const int max_rounds = h * w + 16;  // a converged round changes nothing; the cap guards a bug
     const int s = wave >> 2;
+#ifdef GS_SPEC_ROOM
+    const int dir = DIR >= 0 ? DIR : (wave + 2 * s) & 3;
+#else
     const int dir = (wave + 2 * s) & 3;
+#endif
     const bool ok = __builtin_amdgcn_readfirstlane(sh.src_ok[s]) != 0;
     unsigned *word = reinterpret_cast<unsigned *>(sh.changed[s]);
     unsigned *tmo = &sh.bar[2 + s][2];
@@ -1596,6 +1610,26 @@ __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
             break;
         }
     }
+}
+#endif
+
+#ifdef GS_SPEC_ROOM
+// A room-class instance's rounds: each sweep wave branches once, on its wave-uniform direction, into
+// the rounds loop instantiated for it.  (SIMAPS_SPEC_NO_DIR_ROUNDS: the room fixed, the direction not.)
+template <int RH, int RW>
+__device__ __forceinline__ void sssp_rounds_room(Shared &sh, float *dist)
+{
+#ifdef GS_SPEC_DIR_ROUNDS
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    switch ((wave + 2 * (wave >> 2)) & 3) {  // sssp_rounds_word's own dir
+    case 0: sssp_rounds_word<0, RH, RW>(sh, dist); break;
+    case 1: sssp_rounds_word<1, RH, RW>(sh, dist); break;
+    case 2: sssp_rounds_word<2, RH, RW>(sh, dist); break;
+    default: sssp_rounds_word<3, RH, RW>(sh, dist); break;
+    }
+#else
+    sssp_rounds_word<-1, RH, RW>(sh, dist);
+#endif
 }
 #endif
 
@@ -2580,7 +2614,11 @@ __device__ __forceinline__ void dump_dist(const Shared &sh, const float *dist, f
 // cspace (OccupancyMap.update, envs.py:2453-2454) -> snapped sources (envs.py:2514-2517, 2523-2524)
 // -> distance arrays; then the cspace scratch is released to the render group's raster tile and
 // the sweeps run to the fixpoint (GridGraph._spfa, pyx:69-114), finish and scale in place.
+#ifdef GS_SPEC_ROOM  // (simaps_spec.hip: RH x RW the room of a room-class instance, 0 where it is a run-time value)
+template <int G, int RH = 0, int RW = 0>
+#else
 template <int G>
+#endif
 __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *dist, const simaps_config &cfg,
                                             const Geometry &geo, const simaps_agent &ag, const simaps_env &ev,
                                             const simaps_robot *__restrict__ robots,
@@ -2650,7 +2688,10 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
         STAMP_NB(3);
     }
     if (nsrc == 0) return;
-#ifdef GS_SPEC_ROUND_WORD
+#if defined(GS_SPEC_ROOM)
+    if constexpr (RH != 0) sssp_rounds_room<RH, RW>(sh, dist);
+    else sssp_rounds_word(sh, dist);
+#elif defined(GS_SPEC_ROUND_WORD)
     sssp_rounds_word(sh, dist);
 #else
     sssp_rounds(sh, dist, nsrc, g);

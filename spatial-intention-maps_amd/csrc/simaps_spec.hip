@@ -4,7 +4,8 @@
 // another name and gives the body a local `cfg` whose fixed fields are constants: every helper is
 // __forceinline__ and takes cfg by reference, so the constants fold through render_maps,
 // render_distance_channels, RenderCtx::put, sweep_track and the nsrc / cs_waves / nw decisions.
-// Room rect, H / W, thickness, encodings, scales and rotate_rounding stay run-time values.  Built
+// Room rect, H / W, thickness, encodings, scales and rotate_rounding stay run-time values in S1 / S2;
+// their room-class twins (GS_SPEC_ROOM below) fix H / W and the room's size too.  Built
 // into libsimaps.so beside simaps.hip, whose device helpers it includes (SIMAPS_DEVICE_ONLY).
 //
 // With the flags fixed the render track ends about 3 us before the sweep track,
@@ -44,13 +45,31 @@
 #if defined(GS_SPEC_RENDER_ZERO) && !defined(SIMAPS_SPEC_NO_EARLY_ZERO)
 #define GS_SPEC_EARLY_ZERO
 #endif
+// Room-class instances (GS_SPEC_ROOM; spec.h room_class_of): S1 / S2 with the map shape H x W and the
+// room's h x w fixed as well, for the small room of the BASELINE small_* configurations.  Everything
+// derived from them folds: the pitch, len / span / cells per lane of each sweep direction, the cspace
+// row blocks, early_tile / tail_cells and the crop's range checks against the room.  The room's origin
+// and rotate_rounding stay run-time values (a twin per rounding was measured within noise of this and
+// removed: HISTORY.md Appendix I).
+//   GS_SPEC_DIR_ROUNDS   (with GS_SPEC_ROOM) each sweep wave branches once on its direction into a
+//                        rounds loop instantiated for it (sssp_rounds_room / sssp_rounds_word<DIR>)
+// They take the early occupancy loads and the round words as given (no room instances without them).
+#if !defined(SIMAPS_SPEC_NO_ROOM) && defined(GS_SPEC_ROUND_WORD) && defined(GS_SPEC_EARLY_OCC)
+#define GS_SPEC_ROOM
+#ifndef SIMAPS_SPEC_NO_DIR_ROUNDS
+#define GS_SPEC_DIR_ROUNDS
+#endif
+#define GS_ROOM_H RH
+#define GS_ROOM_W RW
+#endif
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
 #include "spec.h"
 
 namespace {
 // REC: use_shortest_path_to_receptacle_map (S1: 1, S2: 0)
-template <int REC>
+// MH x MW / RH x RW: the room class's map shape and room, 0 for S1 / S2 themselves (run-time values)
+template <int REC, int MH = 0, int MW = 0, int RH = 0, int RW = 0>
 __global__ void __launch_bounds__(NT) get_state_spec_kernel(
     simaps_config cfg_in, Geometry geo, const simaps_agent *__restrict__ agents, const simaps_env *__restrict__ envs,
     const simaps_robot *__restrict__ robots, const double *__restrict__ paths, const uint8_t *__restrict__ occupancy,
@@ -65,11 +84,22 @@ __global__ void __launch_bounds__(NT) get_state_spec_kernel(
     cfg.use_history_map = 0;
     cfg.use_intention_channels = 0;
     cfg.layout_chw = 1;
+#ifdef GS_SPEC_ROOM
+    if (RH) {
+        cfg.H = MH;
+        cfg.W = MW;
+        cfg.room_h = RH;
+        cfg.room_w = RW;
+    }
+#endif
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #include "get_state_body.inc"
 #undef GS_MIXED
 }
+
+using spec_kernel_t = void (*)(simaps_config, Geometry, const simaps_agent *, const simaps_env *, const simaps_robot *,
+                               const double *, const uint8_t *, const float *, float *, int, unsigned *);
 }  // namespace
 
 namespace simaps_spec {
@@ -78,12 +108,16 @@ void launch_get_state(int id, const simaps_config &cfg, const simaps::Geometry &
                       const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
                       hipStream_t stream)
 {
-    if (id == SIMAPS_SPEC_S1)
-        hipLaunchKernelGGL(get_state_spec_kernel<1>, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths,
-                           occupancy, overhead, state, C, fault);
-    else
-        hipLaunchKernelGGL(get_state_spec_kernel<0>, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths,
-                           occupancy, overhead, state, C, fault);
+    spec_kernel_t k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1> : get_state_spec_kernel<0>;
+#ifdef GS_SPEC_ROOM
+    // the room-class twin of S1 / S2 where cfg's shape matches a class exactly (spec.h)
+    if (room_class_of(cfg) == SIMAPS_ROOM_SMALL) {
+        constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
+        k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1, MH, MW, RH, RW> : get_state_spec_kernel<0, MH, MW, RH, RW>;
+    }
+#endif
+    hipLaunchKernelGGL(k, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy, overhead,
+                       state, C, fault);
 }
 
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
@@ -93,3 +127,18 @@ int read_stamps(unsigned long long *host_out)
 }
 #endif
 }  // namespace simaps_spec
+
+extern "C" {
+int simaps_spec_room_abi_version(void) { return SIMAPS_SPEC_ROOM_ABI_VERSION; }
+
+int simaps_get_state_room_class(const simaps_config *cfg, int has_debug)
+{
+    if (!cfg) return SIMAPS_EINVAL;
+#ifdef GS_SPEC_ROOM
+    if (simaps_spec::instance_of(*cfg, has_debug != 0) == SIMAPS_SPEC_GENERIC) return SIMAPS_ROOM_NONE;
+    return simaps_spec::room_class_of(*cfg);
+#else
+    return SIMAPS_ROOM_NONE;  // (an A/B build without the room instances)
+#endif
+}
+}

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "geom.h"
 #include "simaps_spec.h"
+#include "simaps_spec_room.h"
 
 namespace simaps_spec {
 // The instance whose fixed fields match cfg, by truthiness as the device code tests them
@@ -15,6 +16,16 @@ inline int instance_of(const simaps_config &c, bool has_debug)
         !c.use_intention_map || c.use_history_map || c.use_intention_channels || !c.layout_chw)
         return SIMAPS_SPEC_GENERIC;
     return c.use_shortest_path_to_receptacle_map ? SIMAPS_SPEC_S1 : SIMAPS_SPEC_S2;
+}
+
+// The room class (include/simaps_spec_room.h) whose map shape and room equal cfg's exactly; the
+// caller has found instance_of(cfg, ...) to be S1 or S2.
+inline int room_class_of(const simaps_config &c)
+{
+    if (c.H == SIMAPS_ROOM_SMALL_H && c.W == SIMAPS_ROOM_SMALL_W && c.room_h == SIMAPS_ROOM_SMALL_RH &&
+        c.room_w == SIMAPS_ROOM_SMALL_RW)
+        return SIMAPS_ROOM_SMALL;
+    return SIMAPS_ROOM_NONE;
 }
 
 inline bool any_debug(const simaps_debug &d)

@@ -1,5 +1,5 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
-include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h,
+include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h, include/simaps_spec_room.h,
 include/simaps_ingest_seq.h and include/simaps_action_as.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
@@ -131,6 +131,13 @@ EXPORTED_SPEC = ('simaps_spec_abi_version', 'simaps_get_state_instance')
 SPEC_ABI_VERSION = 1  # SIMAPS_SPEC_ABI_VERSION
 SPEC_GENERIC, SPEC_S1, SPEC_S2 = 0, 1, 2  # SIMAPS_SPEC_*
 SPEC_NAMES = {SPEC_GENERIC: 'generic', SPEC_S1: 'S1', SPEC_S2: 'S2'}
+
+# include/simaps_spec_room.h: the room class of the instance a get_state call takes (host-only query)
+EXPORTED_SPEC_ROOM = ('simaps_spec_room_abi_version', 'simaps_get_state_room_class')
+SPEC_ROOM_ABI_VERSION = 1  # SIMAPS_SPEC_ROOM_ABI_VERSION
+ROOM_NONE, ROOM_SMALL = 0, 1  # SIMAPS_ROOM_*
+ROOM_NAMES = {ROOM_NONE: 'none', ROOM_SMALL: 'small'}
+ROOM_SMALL_SHAPE = (184, 232, 44, 92)  # SIMAPS_ROOM_SMALL_H / _W / _RH / _RW
 
 
 # include/simaps_ingest_seq.h: several frames per map slot in one launch, applied in order (with its
@@ -267,6 +274,14 @@ def _load(path=LIB_PATH):
         if vk != SPEC_ABI_VERSION:
             raise ImportError('libsimaps spec ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vk, SPEC_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_room_class'):  # (include/simaps_spec_room.h; absent only in an older revision's A/B build)
+        L.simaps_spec_room_abi_version.restype = i32
+        L.simaps_get_state_room_class.argtypes = [ctypes.POINTER(Config), i32]
+        L.simaps_get_state_room_class.restype = i32
+        vr = L.simaps_spec_room_abi_version()
+        if vr != SPEC_ROOM_ABI_VERSION:
+            raise ImportError('libsimaps spec_room ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vr, SPEC_ROOM_ABI_VERSION))
     if hasattr(L, 'simaps_ingest_seq'):  # (include/simaps_ingest_seq.h; absent only in an older revision's A/B build)
         L.simaps_ingest_seq_abi_version.restype = i32
         # simaps_ingest's list with seq and num_seq after seg_raw

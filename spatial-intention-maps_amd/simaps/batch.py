@@ -390,6 +390,16 @@ class StateBatch(_ArrayUpload):
         has_dbg = bool(debug) or (self._rec is not None and bool(self.flags['use_shortest_path_to_receptacle_map']))
         return _lib.lib.simaps_get_state_instance(self.cfg, int(has_dbg))
 
+    def room_class(self, debug=False):
+        """SIMAPS_ROOM_* class of the instance a float32 render() takes (include/simaps_spec_room.h):
+        the twin of kernel_instance()'s S1 / S2 with the map shape and the room's size fixed too
+        where the configuration's equal a class's exactly, 0 = none (S1 / S2 / the generic kernel
+        as kernel_instance() says)."""
+        if isinstance(debug, dict):
+            debug = any(v is not None for v in debug.values())
+        has_dbg = bool(debug) or (self._rec is not None and bool(self.flags['use_shortest_path_to_receptacle_map']))
+        return _lib.lib.simaps_get_state_room_class(self.cfg, int(has_dbg))
+
     def render(self, out=None, debug=None, stream=None, slots=None, dtype=None):
         """Launch the fused kernel: the stacks of every agent (or of map slots `slots`, in that
         order) into `out` (allocated if None).  Asynchronous on `stream` (default: the current
