@@ -17,8 +17,9 @@
  * A call of S1 / S2 whose H, W, room_h and room_w equal the small room's exactly launches that
  * instance's twin with those four fixed as well; the id reported here stays S1 / S2.
  *
- * simaps_get_state_as (16-bit stacks), simaps_get_state_into and the mixed launches always take
- * their own generic kernels.
+ * simaps_get_state_as (16-bit stacks) and simaps_get_state_into take instances of their own by the
+ * same rule (simaps_spec_store.h has their queries); the mixed launches always take their own
+ * generic kernels.
  *
  * The query below is host-only: it launches nothing and needs no GPU.
  */

@@ -5,7 +5,8 @@
 // exactly those of the single-configuration kernel.)  With SIMAPS_STATE16 (simaps_state16.inc) state
 // is the 16-bit stack and RenderCtx converts at the store; nothing else differs.  With GS_INTO
 // (simaps_store.inc, GS_MIXED 0) the stack goes to row into_row of the caller's store and faults are
-// posted under SIMAPS_K_GET_STATE_INTO.
+// posted under SIMAPS_K_GET_STATE_INTO (or under GS_INTO_KID where the includer defines it:
+// simaps_spec_store.inc, whose 16-bit kernels serve simaps_get_state_as too).
 #if defined(SIMAPS_VGPR_CAP) && !GS_MIXED  // (timing-only A/B build: the LDS hidden from the occupancy estimate)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #else
@@ -261,7 +262,9 @@
     }
     if (tid == 0) {
         const unsigned f = group_faults(sh.bar, sh.rounds, nsrc);
-#ifdef GS_INTO
+#if defined(GS_INTO) && defined(GS_INTO_KID)  // (simaps_spec_store.inc: one kernel for the store launch and the plain 16-bit one)
+        post_faults(fault, f, GS_INTO_KID, n);
+#elif defined(GS_INTO)
         post_faults(fault, f, SIMAPS_K_GET_STATE_INTO, n);
 #else
         post_faults(fault, f, GS_MIXED ? SIMAPS_K_GET_STATE_MIXED : SIMAPS_K_GET_STATE, n);

@@ -52,6 +52,7 @@
 #include "simaps_state16.h"
 #include "simaps_store.h"
 #include "spec.h"
+#include "spec_store.h"
 #include "state16.h"
 #include "store.h"
 
@@ -4691,6 +4692,26 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     simaps_debug d;
     memset(&d, 0, sizeof(d));
     if (dbg) d = *dbg;
+#ifndef SIMAPS_VGPR_CAP
+    // the store launches and the 16-bit launches: a compile-time instance where one matches the call
+    // (simaps_spec_store.h, simaps_spec_store.inc); dest == nullptr is simaps_get_state_as
+    if (dest || state_dtype != SIMAPS_STATE_F32) {
+        const int inst = simaps_spec_store::instance_as(*cfg, state_dtype, dest != nullptr, simaps_spec::any_debug(d));
+        if (inst != SIMAPS_SPEC_GENERIC) {
+            if (state_dtype == SIMAPS_STATE_F32)
+                simaps_spec_store::launch_f32(inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
+                                              (float *)state, capacity, dest, C, cx.fault_dev, (hipStream_t)stream);
+            else
+                (state_dtype == SIMAPS_STATE_BF16 ? simaps_spec_store::launch_bf16 : simaps_spec_store::launch_f16)(
+                    inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity,
+                    dest, C, cx.fault_dev, (hipStream_t)stream);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess)
+                return fail(SIMAPS_EHIP, "%s launch: %s", dest ? "get_state_into" : "get_state_as", hipGetErrorString(e));
+            return 0;
+        }
+    }
+#endif
     if (dest) {  // simaps_get_state_into: one launch of the element type's kernel (simaps_store.inc)
         if (state_dtype == SIMAPS_STATE_F32)
             simaps_store::launch_get_state_into_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,

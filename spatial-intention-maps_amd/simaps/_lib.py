@@ -1,6 +1,6 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
 include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h, include/simaps_spec_room.h,
-include/simaps_ingest_seq.h and include/simaps_action_as.h).
+include/simaps_spec_store.h, include/simaps_ingest_seq.h and include/simaps_action_as.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -138,6 +138,11 @@ SPEC_ROOM_ABI_VERSION = 1  # SIMAPS_SPEC_ROOM_ABI_VERSION
 ROOM_NONE, ROOM_SMALL = 0, 1  # SIMAPS_ROOM_*
 ROOM_NAMES = {ROOM_NONE: 'none', ROOM_SMALL: 'small'}
 ROOM_SMALL_SHAPE = (184, 232, 44, 92)  # SIMAPS_ROOM_SMALL_H / _W / _RH / _RW
+
+# include/simaps_spec_store.h: the same two answers for the store launches and the 16-bit launches
+EXPORTED_SPEC_STORE = ('simaps_spec_store_abi_version', 'simaps_get_state_instance_as',
+                       'simaps_get_state_room_class_as')
+SPEC_STORE_ABI_VERSION = 1  # SIMAPS_SPEC_STORE_ABI_VERSION
 
 
 # include/simaps_ingest_seq.h: several frames per map slot in one launch, applied in order (with its
@@ -282,6 +287,15 @@ def _load(path=LIB_PATH):
         if vr != SPEC_ROOM_ABI_VERSION:
             raise ImportError('libsimaps spec_room ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vr, SPEC_ROOM_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_instance_as'):  # (include/simaps_spec_store.h; absent only in an older revision's A/B build)
+        L.simaps_spec_store_abi_version.restype = i32
+        for f in (L.simaps_get_state_instance_as, L.simaps_get_state_room_class_as):
+            f.argtypes = [ctypes.POINTER(Config), i32, i32, i32]
+            f.restype = i32
+        vs = L.simaps_spec_store_abi_version()
+        if vs != SPEC_STORE_ABI_VERSION:
+            raise ImportError('libsimaps spec_store ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vs, SPEC_STORE_ABI_VERSION))
     if hasattr(L, 'simaps_ingest_seq'):  # (include/simaps_ingest_seq.h; absent only in an older revision's A/B build)
         L.simaps_ingest_seq_abi_version.restype = i32
         # simaps_ingest's list with seq and num_seq after seg_raw

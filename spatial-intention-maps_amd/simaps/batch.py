@@ -241,6 +241,15 @@ class ActionResult:
         return out
 
 
+def _has_debug(b, debug, into):
+    """has_debug as the library sees the launch of batch b: a debug buffer, or (render() only:
+    render_into() never passes it) the enabled receptacle cache of a stack that has its map."""
+    if isinstance(debug, dict):
+        debug = any(v is not None for v in debug.values())
+    rec = not into and b._rec is not None and bool(b.flags['use_shortest_path_to_receptacle_map'])
+    return int(bool(debug) or rec)
+
+
 class StateBatch(_ArrayUpload):
     """One configuration's batch of agent-state stacks, resident on `device`.
 
@@ -381,24 +390,26 @@ class StateBatch(_ArrayUpload):
         return {'cspace': z(n, h, w, dt=torch.uint8), 'sources': z(n, 2, 4, dt=torch.int32),
                 'dist': z(n, 2, h, w, dt=torch.float32), 'status': z(n, dt=torch.int32)}
 
-    def kernel_instance(self, debug=False):
-        """SIMAPS_SPEC_* id of the kernel a float32 render() takes (include/simaps_spec.h): a
-        compile-time instance for the standard stacks, 0 = the generic kernel -- always with debug
-        outputs or an enabled receptacle cache."""
-        if isinstance(debug, dict):
-            debug = any(v is not None for v in debug.values())
-        has_dbg = bool(debug) or (self._rec is not None and bool(self.flags['use_shortest_path_to_receptacle_map']))
-        return _lib.lib.simaps_get_state_instance(self.cfg, int(has_dbg))
+    def kernel_instance(self, debug=False, dtype=None, into=False):
+        """SIMAPS_SPEC_* id of the kernel a render() takes (include/simaps_spec.h,
+        include/simaps_spec_store.h): a compile-time instance for the standard stacks, 0 = the
+        generic kernel -- always with debug outputs or, in render(), an enabled receptacle cache.
+        dtype: the stack's element type (default float32); into=True: render_into() of a store of
+        that dtype, which never passes the receptacle cache."""
+        if dtype is None and not into:
+            return _lib.lib.simaps_get_state_instance(self.cfg, _has_debug(self, debug, False))
+        return _lib.lib.simaps_get_state_instance_as(self.cfg, _lib.state_dtype_id(dtype or torch.float32),
+                                                     int(bool(into)), _has_debug(self, debug, into))
 
-    def room_class(self, debug=False):
-        """SIMAPS_ROOM_* class of the instance a float32 render() takes (include/simaps_spec_room.h):
-        the twin of kernel_instance()'s S1 / S2 with the map shape and the room's size fixed too
-        where the configuration's equal a class's exactly, 0 = none (S1 / S2 / the generic kernel
-        as kernel_instance() says)."""
-        if isinstance(debug, dict):
-            debug = any(v is not None for v in debug.values())
-        has_dbg = bool(debug) or (self._rec is not None and bool(self.flags['use_shortest_path_to_receptacle_map']))
-        return _lib.lib.simaps_get_state_room_class(self.cfg, int(has_dbg))
+    def room_class(self, debug=False, dtype=None, into=False):
+        """SIMAPS_ROOM_* class of the instance that launch takes (include/simaps_spec_room.h,
+        include/simaps_spec_store.h): the twin of kernel_instance()'s S1 / S2 with the map shape and
+        the room's size fixed too where the configuration's equal a class's exactly, 0 = none
+        (S1 / S2 / the generic kernel as kernel_instance() says)."""
+        if dtype is None and not into:
+            return _lib.lib.simaps_get_state_room_class(self.cfg, _has_debug(self, debug, False))
+        return _lib.lib.simaps_get_state_room_class_as(self.cfg, _lib.state_dtype_id(dtype or torch.float32),
+                                                       int(bool(into)), _has_debug(self, debug, into))
 
     def render(self, out=None, debug=None, stream=None, slots=None, dtype=None):
         """Launch the fused kernel: the stacks of every agent (or of map slots `slots`, in that
