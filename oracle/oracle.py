@@ -540,7 +540,11 @@ class AgentOracle:
         me = self.robot
         dists = [distance(me['position'], r['position']) for r in self.scene['robots']]
         chans = []
-        for i in np.argsort(dists):
+        # Equal distances: the reference's np.argsort(dists) (envs.py:2353) is numpy's insertion sort for
+        # so few elements -- index order -- unless numpy dispatches a SIMD argsort (AVX-512 from numpy
+        # 1.25, AVX2 from 2.0), whose tie order is neither stable nor the same across hosts.  The rule
+        # here is the index order, on every host (scene_dense_ties_8.npz pins it to the reference).
+        for i in np.argsort(dists, kind='stable'):
             r = self.scene['robots'][i]
             if i == self.a:
                 continue

@@ -5,6 +5,9 @@ scikit-image 0.18.3).  Run:
 
     make -C oracle ref                                   # reference Cython SPFA -> oracle/_ref/
     env -u PYTHONPATH /opt/conda/bin/python3.9 tests/golden/make_goldens.py
+    # the dense goldens hold exact distance ties: on a host whose numpy has a SIMD argsort
+    NPY_DISABLE_CPU_FEATURES="AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512_SPR" \
+        env -u PYTHONPATH /opt/conda/bin/python3.9 tests/golden/make_goldens.py dense
 
 What runs is UNMODIFIED reference code: envs.Mapper / envs.OccupancyMap (envs.py:2010-2555)
 and GridGraph compiled from /root/reference/shortest_paths/shortest_paths.pyx.  To import
@@ -35,6 +38,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 REF = os.environ.get('SIMAPS_REFERENCE', '/root/reference')
 sys.path.insert(0, os.path.join(REPO, 'spatial-intention-maps_amd'))
 sys.path.insert(0, os.path.join(REPO, 'oracle'))
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 from simaps import constants as K  # noqa: E402
 from simaps import synthetic  # noqa: E402
 
@@ -247,6 +251,28 @@ def gen_rot_scenes(envs):
                 r['heading'] = h
             scenes.append(dict(sc, rotate_rounding=host))
         write_scene_golden(envs, 'rot-%s_%s' % (host, cfg), scenes, lambda sc: list(range(len(sc['robots']))))
+
+
+# numpy features whose dispatch brings a SIMD argsort (numpy 1.26: AVX-512 only)
+NO_SIMD_ARGSORT = 'AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512_SPR'
+
+
+def gen_dense(envs):
+    """scene_dense_<case>.npz: scenes at the descriptor limits (tests/dense_scenes.py: 8 robots, 16-point
+    paths, every segment slot; 5 robots; exact distance ties), env 0 of each, rendered by the reference
+    for its first and its last robot.  They pin the oracle at the sizes tests/test_gpu_dense.py then
+    holds the kernels to."""
+    import dense_scenes
+    # ties_8 holds exactly equal distances, which Mapper._get_intention_channels orders with np.argsort
+    # (envs.py:2353): index order with numpy's own insertion sort, anything with a SIMD argsort
+    x = [0.25, 0.4, 0.0, 0.0, 0.3, 0.25, 0.0, 0.1]
+    if np.argsort(x).tolist() != np.argsort(x, kind='stable').tolist():
+        raise RuntimeError('np.argsort breaks ties out of index order here (a SIMD argsort): run the dense goldens '
+                           'with NPY_DISABLE_CPU_FEATURES="%s"' % NO_SIMD_ARGSORT)
+    host = K.host_rotate_rounding()
+    for name in dense_scenes.GOLDEN_CASES:
+        scenes = [dict(dense_scenes.build(name, 0), rotate_rounding=host)]
+        write_scene_golden(envs, dense_scenes.config_name(name), scenes, lambda sc: [0, len(sc['robots']) - 1])
 
 
 def write_rotate(rs):
@@ -636,6 +662,8 @@ def main():
         gen_rotate()
     if 'rot_scenes' in which or not sys.argv[1:]:
         gen_rot_scenes(envs)
+    if 'dense' in which or not sys.argv[1:]:
+        gen_dense(envs)
 
 
 if __name__ == '__main__':
