@@ -7,11 +7,7 @@
 // (simaps_store.inc, GS_MIXED 0) the stack goes to row into_row of the caller's store and faults are
 // posted under SIMAPS_K_GET_STATE_INTO (or under GS_INTO_KID where the includer defines it:
 // simaps_spec_store.inc, whose 16-bit kernels serve simaps_get_state_as too).
-#if defined(SIMAPS_VGPR_CAP) && !GS_MIXED  // (timing-only A/B build: the LDS hidden from the occupancy estimate)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-#else
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-#endif
     Shared &sh = *reinterpret_cast<Shared *>(smem);
     float *dist = reinterpret_cast<float *>(smem + OFF_DIST);
     SsspScratch &S = *reinterpret_cast<SsspScratch *>(smem + OFF_UNION);
@@ -39,7 +35,7 @@
                             tail_cells_off(cfg.room_h, cfg.room_w) + LW * LW * 2 <= DIST_FLOATS * 4;
     if (tid < 16) (&sh.bar[0][0])[tid] = 0u;
     if (tid == 16) sh.scratch_free = cs_waves == 0;
-#if defined(GS_SPEC_EARLY_OCC) && !GS_MIXED
+#if defined(GS_SPEC) && !GS_MIXED  // GS_SPEC_EARLY_OCC
     // (simaps_spec.hip: the sweep waves' occupancy loads need the agent record only, so they are
     // issued here, ahead of the env record and the entry barrier, and handed to sweep_track)
     OccLoad4<512> pre8;
@@ -90,18 +86,15 @@
         const uint8_t *occ_base = occupancy + ((int64_t)map_off[ag.map_slot] - (int64_t)ag.map_slot * H * W);
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
-#elif defined(GS_SPEC_ROOM)  // (simaps_spec.hip: GS_ROOM_H x GS_ROOM_W the instance's compile-time room, 0 in S1 / S2)
+#elif defined(GS_SPEC)  // GS_SPEC_ROOM (simaps_spec.hip: GS_ROOM_H x GS_ROOM_W the instance's compile-time room, 0 in
+                       // S1 / S2) and GS_SPEC_EARLY_OCC (a sweep wave: pre_occ is sweep_track's own use4, so the
+                       // loads are there when it wants them)
         if (cs_waves == 8)
             sweep_track<512, GS_ROOM_H, GS_ROOM_W>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g,
                                                    early_tile, &pre8);
         else
             sweep_track<256, GS_ROOM_H, GS_ROOM_W>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g,
                                                    early_tile, &pre4);
-#elif defined(GS_SPEC_EARLY_OCC)  // (a sweep wave: pre_occ is sweep_track's own use4, so the loads are there when it wants them)
-        if (cs_waves == 8)
-            sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile, &pre8);
-        else
-            sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile, &pre4);
 #else
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
@@ -219,7 +212,7 @@
                 }
             }
         }
-#if defined(GS_SPEC_EARLY_ZERO) && defined(GS_SPEC_RENDER_ZERO)
+#ifdef GS_SPEC  // GS_SPEC_EARLY_ZERO (with GS_SPEC_RENDER_ZERO)
         // (simaps_spec.hip, two sources: the sweep track has usually released its scratch by now, so
         // each render wave zeroes its share of the tile's first SCRATCH_Q words ahead of the barrier
         // below, which the stamps need anyway, and the first raster pass starts without one of its

@@ -22,15 +22,9 @@
 // Padded layout per query: (wh + 2) rows x pitch = ww + 2 columns, border and blocked cells -inf,
 // free cells +inf until reached.
 
-#ifndef SIMAPS_GL_WPD
-#define SIMAPS_GL_WPD 1
-#endif
-constexpr int GL_WPD = SIMAPS_GL_WPD;  // gl_sssp_kernel: waves per sweep direction (each takes every
+constexpr int GL_WPD = 1;  // gl_sssp_kernel: waves per sweep direction (each takes every
 constexpr int GL_NT = 4 * 64 * GL_WPD;  //  GL_WPD-th 64-cell strip of its direction's lines)
-#ifndef SIMAPS_GL_PF
-#define SIMAPS_GL_PF 32
-#endif
-constexpr int GL_PF = SIMAPS_GL_PF;  // lines prefetched ahead in a sweep strip
+constexpr int GL_PF = 32;  // lines prefetched ahead in a sweep strip
 constexpr int GL_INQ = 16;  // pin bit 4: in the queue (bits 0-3: 1 + direction of the parent edge)
 constexpr int GL_CHECK = 64;  // gl_path_kernel: pops between early-exit checks
 

@@ -4,9 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef SIMAPS_PHILOX_HD
 #define SIMAPS_PHILOX_HD __host__ __device__ __forceinline__
-#endif
 
 namespace simaps_philox {
 // out = Philox4x32-10(counter c, key k)

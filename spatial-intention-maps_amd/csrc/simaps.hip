@@ -34,9 +34,10 @@
 //
 // Diagnostic-only build macros (never the product): SIMAPS_PHASE_STAMPS / SIMAPS_LIGHT_STAMPS
 // (per-phase s_memrealtime stamps, tools/phase_profile.py, `make prof`), SIMAPS_DIAG_FLAG_TIMEOUT
-// (the fault-path test build, `make diag`).  The round-1/2 ablation variants (sweeps or render
-// alone, no gathers / raster / stores, issue-priority variants) were measured and removed; their
-// results are in DESIGN.md.
+// (the fault-path test build, `make diag`); the table at the top of the Makefile lists every switch
+// a command line can set.  The round-1/2 ablation variants (sweeps or render alone, no gathers /
+// raster / stores, issue-priority variants) and the later A/B switches whose experiments were decided
+// were measured and removed; their results are in DESIGN.md.
 //
 // Compiled with -ffp-contract=off: every fp32/fp64 operation rounds exactly like the reference
 // (see geom.h for the one explicit fma).
@@ -68,11 +69,7 @@ constexpr int NT = 1024;
 constexpr int MAX_STAMP_WG = 8192, NSTAMP = 80;
 __device__ unsigned long long g_stamps[MAX_STAMP_WG * NSTAMP];
 #ifdef SIMAPS_LIGHT_STAMPS
-#ifdef SIMAPS_LIGHT_SET
-#define STAMP_ON(k) (SIMAPS_LIGHT_SET(k))
-#else
 #define STAMP_ON(k) ((k) == 0 || (k) == 7 || (k) == 8 || (k) == 11 || (k) == 13 || (k) == 60 || (k) == 61 || (k) == 62)
-#endif
 #define STAMP_BAR()
 #else
 #define STAMP_ON(k) true
@@ -1211,20 +1208,14 @@ __device__ __forceinline__ void mark_range(uint64_t *m, int a, int b)  // bits a
     mark_lines(m, a <= 63 ? bits64(a, min(b, 63)) : 0ull, b >= 64 ? bits64(max(a, 64) - 64, b - 64) : 0ull);
 }
 
-// SSSP_CHECK: the rounds end with the fixpoint check below (sssp_check) instead of inline marks.
-#ifdef SIMAPS_SSSP_CHECK
-constexpr bool SSSP_CHECK = true;   // (A/B build: measured slower, HISTORY.md Appendix C)
-#else
-constexpr bool SSSP_CHECK = false;  // the product: inline marks + a confirming round
-#endif
-
 // One sweep of direction dir_in over source dm's array; true if it improved a cell.  With nparts > 1
 // (compile-time pitch only) the sweep covers part `part` of the direction's steps: it relaxes out of
 // the lines of steps [s0, s1) (their dirty bits are its own) and into the line of step s1, which the
 // next part relaxes out of -- marked dirty for it when this part improved that line.
-constexpr bool SSSP_INLINE_MARKS = !SSSP_CHECK;
+// A sweep marks, inline, the lines that the other directions have to relax out of again, and the rounds
+// end with a confirming round (see "the fixpoint check" below for the alternative that was measured).
 __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_in, uint64_t (*dm)[2], int &steps,
-                                      int part = 0, int nparts = 1, bool marks = SSSP_INLINE_MARKS,
+                                      int part = 0, int nparts = 1,
                                       unsigned long long *clk = nullptr)  // (stamp build: clocks around the asm loop)
 {
     lds_float *D = (lds_float *)Dg;  // the distance arrays live in LDS: keep ds_* addressing
@@ -1274,13 +1265,13 @@ __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_i
         }
         steps += o.steps;
         if (clk) clk[1] = __builtin_amdgcn_s_memtime();
-#ifdef GS_SPEC_FLAT_MARKS  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
+#ifdef GS_SPEC  // GS_SPEC_FLAT_MARKS (simaps_spec.hip: the compile-time instances of get_state_kernel only)
         // The same marks as below without the lane-0 diamonds: the operands are wave-uniform and
         // zero where nothing improved (an OR with 0 changes nothing), and six lanes issue the six
         // non-returning 64-bit ORs as one LDS instruction.  They still follow the sweep's writes in the wave's
         // LDS order (its asm drained them) and precede the wave's arrival at the round's barrier, so
         // a decrease is either seen by a later snapshot's sweep or left marked.
-        if (marks && nparts == 1) {
+        if (nparts == 1) {
             const bool any = o.lanes != 0;
             const int a = max(fwd ? o.imin : len - 1 - o.imax, 0), b = min(fwd ? o.imax : len - 1 - o.imin, 127);
             const bool rng = any && a <= b;
@@ -1301,7 +1292,7 @@ __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_i
         }
 #endif
         if (!o.lanes) return false;
-        if (marks && lane == 0) {
+        if (lane == 0) {
             const int a = fwd ? o.imin : len - 1 - o.imax, b = fwd ? o.imax : len - 1 - o.imin;
             mark_range(dm[dir ^ 1], max(a, 0), min(b, 127));
             if (s1 < len && o.imax >= s1) {  // improved the next part's first line: its to relax out of
@@ -1325,123 +1316,25 @@ __device__ __forceinline__ bool sweep(float *Dg, int h, int w, int pw, int dir_i
     case 2: chg = h <= 63 ? sweep_t<2, 1, 0>(D, w, h, pw) : sweep_t<2, 2, 0>(D, w, h, pw); break;
     default: chg = h <= 63 ? sweep_t<3, 1, 0>(D, w, h, pw) : sweep_t<3, 2, 0>(D, w, h, pw); break;
     }
-    if (marks && chg && lane == 0)
+    if (chg && lane == 0)
         for (int d2 = 0; d2 < 4; d2++)
             if (d2 != dir) mark_range(dm[d2], 0, (d2 < 2 ? h : w) - 1);
     return chg;
 }
 
-// ---- the fixpoint check (round 4) -----------------------------------------------------------------
-// After a round's sweeps (behind their barrier), one lane-parallel pass tests EVERY edge into every
-// cell, fl(|d_u| + w) < d_v -- the relaxation a sweep step performs -- which is the fixpoint
-// condition itself.  A cell with a violated edge marks every line such an edge can come out of
-// (the rows above / below for the down / up sweeps, which relax the straight and both diagonal
-// edges out of a row; the columns left / right for the right / left sweeps).  The next round
-// sweeps only from those lines, and a round whose check finds no violated edge has reached the unique f32 fixpoint, so
-// no confirmation round runs and a sweep leaves no marks behind (SSSP_CHECK; the inline marks
-// are supersets: a lowered line is re-swept in the opposite direction whether or not anything
-// there can improve).  Modelled first (tools/sssp_sched_sim.py: -29 % of the slowest sweep chain
-// at an assumed ~1,500-cycle check) and built: bitwise, 3 rounds instead of 4 and -35 % line steps
-// on the BASELINE config, but the check itself costs ~2.2 us per round in the kernel (~25 VALU
+// ---- the fixpoint check (round 4; measured slower, the code is gone) ------------------------------
+// The alternative to the inline marks: after a round's sweeps (behind their barrier), one
+// lane-parallel pass tested EVERY edge into every cell, fl(|d_u| + w) < d_v -- the relaxation a sweep
+// step performs -- which is the fixpoint condition itself.  A cell with a violated edge marked every
+// line such an edge can come out of; the next round swept only from those lines, and a round whose
+// check found no violated edge had reached the unique f32 fixpoint, so no confirmation round ran (the
+// inline marks are supersets: a lowered line is re-swept in the opposite direction whether or not
+// anything there can improve).  Modelled first (tools/sssp_sched_sim.py: -29 % of the slowest sweep
+// chain at an assumed ~1,500-cycle check) and built: bitwise, 3 rounds instead of 4 and -35 % line
+// steps on the BASELINE config, but the check itself cost ~2.2 us per round in the kernel (~25 VALU
 // per row on SIMDs shared with the render waves) plus a second barrier, so every config measured
-// slower (HISTORY.md Appendix C).  Kept as the SIMAPS_SSSP_CHECK A/B build, not the product.
-// Threads t of n (n = 64 * waves, this source's group): lane l owns columns 2l + 1, 2l + 2
-// (w <= 126), wave q a block of rows; returns true (uniform per wave) if this wave found a violation.
-__device__ __forceinline__ uint64_t spread_even(uint32_t x)  // bit i -> bit 2i
-{
-    uint64_t v = x;
-    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
-    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
-    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
-    v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & 0x5555555555555555ull;
-    return v;
-}
-__device__ __forceinline__ bool sssp_check(const float *Dg, int h, int w, int pw, uint64_t (*dm)[2], int t, int n)
-{
-    const lds_float *D = (const lds_float *)Dg;
-    const int lane = t & 63, q = t >> 6, nw = n >> 6;
-    h = __builtin_amdgcn_readfirstlane(h);
-    w = __builtin_amdgcn_readfirstlane(w);
-    pw = __builtin_amdgcn_readfirstlane(pw);
-    // array rows [r0, r1), <= 32 of them (wave-uniform: scalar loop control)
-    const int r0 = __builtin_amdgcn_readfirstlane(1 + q * h / nw), r1 = __builtin_amdgcn_readfirstlane(1 + (q + 1) * h / nw);
-    const bool on0 = 2 * lane + 1 <= w, on1 = 2 * lane + 2 <= w;
-    const int c0 = on0 ? 2 * lane + 1 : 1;  // (idle lanes alias lane 0's cells, masked below)
-    const float s2 = SQRT2F, NI = -INFINITY;
-    // A cell's best candidate over its 8 edges, min(|d_u| + w_uv), against its own value; a violated
-    // cell (r, c) marks the down sweep at row r - 1, the up sweep at row r + 1, the right sweep at
-    // column c - 1 and the left sweep at column c + 1 -- every line a violated edge into it can come
-    // out of (a superset: a sweep that finds nothing there stops after one quiet group).  Per row, the
-    // eight |x| + w of its four cells serve both as its vertical candidates for the rows above and
-    // below and as its horizontal ones.
-    struct RowC {
-        float x0, x1;      // the row's two cells
-        float v0, v1;      // what the row offers the cells (same columns) of the rows above / below
-        float h0, h1;      // the best horizontal candidate of each of its two cells
-    };
-    auto row = [&](int rr) {
-        const lds_float *p = D + rr * pw + c0 - 1;  // columns c0 - 1 .. c0 + 2
-        const float a = p[0], b = p[1], c = p[2], d = p[3];
-        const float a1 = fabsf(a) + 1.0f, b1 = fabsf(b) + 1.0f, c1 = fabsf(c) + 1.0f, d1 = fabsf(d) + 1.0f;
-        const float as = fabsf(a) + s2, bs = fabsf(b) + s2, cs = fabsf(c) + s2, ds = fabsf(d) + s2;
-        RowC o;
-        o.x0 = on0 ? b : NI;  // -inf: never improvable
-        o.x1 = on1 ? c : NI;
-        o.v0 = __builtin_fminf(__builtin_fminf(as, b1), cs);
-        o.v1 = __builtin_fminf(__builtin_fminf(bs, c1), ds);
-        o.h0 = __builtin_fminf(a1, c1);
-        o.h1 = __builtin_fminf(b1, d1);
-        return o;
-    };
-    // rows of this wave in chunks of CK: the CK + 2 rows' loads are issued together (row indices
-    // clamped into the array: a chunk past the wave's last row re-reads row r1, unused), then the
-    // rows' candidates, then the CK checks -- one LDS round trip per chunk instead of one per row
-    constexpr int CK = 8;
-    uint32_t rbits = 0;      // bit (r - r0): row r holds a violated cell
-    uint32_t cvb = 0;        // bit 0 / 1: this lane's column c0 / c0 + 1 holds a violated cell
-    for (int rb = r0; rb < r1; rb += CK) {
-        RowC R[CK + 2];
-#pragma unroll
-        for (int k = 0; k < CK + 2; k++) R[k] = row(min(rb - 1 + k, r1));
-#pragma unroll
-        for (int k = 1; k <= CK; k++) {
-            const int r = rb - 1 + k;
-            const bool e0 = __builtin_fminf(__builtin_fminf(R[k - 1].v0, R[k + 1].v0), R[k].h0) < R[k].x0;
-            const bool e1 = __builtin_fminf(__builtin_fminf(R[k - 1].v1, R[k + 1].v1), R[k].h1) < R[k].x1;
-            const uint32_t e = r < r1 ? (uint32_t)e0 | ((uint32_t)e1 << 1) : 0u;
-            cvb |= e;
-            rbits |= (e != 0u ? 1u : 0u) << (r - r0);
-        }
-    }
-    const bool cv0 = cvb & 1u, cv1 = (cvb >> 1) & 1u;
-    // rows: OR over the wave (DPP reductions), then the marks; columns: ballots
-    uint32_t rb = rbits;
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x111, 0xf, 0xf, false);  // row_shr:1
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x112, 0xf, 0xf, false);  // row_shr:2
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x114, 0xf, 0xf, false);  // row_shr:4
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x118, 0xf, 0xf, false);  // row_shr:8
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    rb |= __builtin_amdgcn_update_dpp(0, rb, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    const uint32_t rows = (uint32_t)__builtin_amdgcn_readlane((int)rb, 63);
-    const uint64_t b0 = __ballot(cv0), b1 = __ballot(cv1);
-    const bool any = (rows | b0 | b1) != 0;
-    if (lane == 0 && any) {
-        // violated row r (bit r - r0) -> down bit (r - 1) - 1 = r - 2, up bit (r + 1) - 1 = r
-        const unsigned __int128 R = (unsigned __int128)rows << (r0 - 1);  // bit r - 1 (r >= 1)
-        const unsigned __int128 Dn = R >> 1, Up = R << 1;
-        // violated column c (lane l: 2l + 1 from b0, 2l + 2 from b1), bit c - 1 = 2l / 2l + 1 -> the
-        // right sweep at column c - 1 (bit c - 2), the left sweep at column c + 1 (bit c)
-        const unsigned __int128 Cc = ((unsigned __int128)spread_even((uint32_t)(b0 >> 32)) << 64 | spread_even((uint32_t)b0)) |
-                                     (((unsigned __int128)spread_even((uint32_t)(b1 >> 32)) << 64 | spread_even((uint32_t)b1)) << 1);
-        const unsigned __int128 Rt = Cc >> 1, Lt = Cc << 1;
-        mark_lines(dm[0], (uint64_t)Dn, (uint64_t)(Dn >> 64));
-        mark_lines(dm[1], (uint64_t)Up, (uint64_t)(Up >> 64));
-        mark_lines(dm[2], (uint64_t)Rt, (uint64_t)(Rt >> 64));
-        mark_lines(dm[3], (uint64_t)Lt, (uint64_t)(Lt >> 64));
-    }
-    return any;
-}
+// slower (HISTORY.md Appendix C).  It stayed as an A/B build for a while and was then removed with
+// its build switch; the history has the code.
 
 // group g: free cells +inf, blocked / border -inf, sources 0 (one pass over the rect rows)
 __device__ __forceinline__ void sssp_init(Shared &sh, const SsspScratch &S, float *dist, int nsrc, const Group &g)
@@ -1507,8 +1400,8 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
     } while (0)
 #endif
 
-#ifdef GS_SPEC_ROUND_WORD  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
-// sssp_rounds with one LDS word per source and round instead of a change flag plus a group barrier.
+#ifdef GS_SPEC  // (simaps_spec.hip: the compile-time instances of get_state_kernel only, down to snap_init_sources)
+// GS_SPEC_ROUND_WORD: sssp_rounds with one LDS word per source and round instead of a change flag plus a group barrier.
 // The storage of sh.changed[s][3] serves as three rotating 32-bit round words.  A wave arrives at
 // round r with one returning add of 1 + (improved << 8) to word r % 3: the value it gets back plus
 // its own addend tells the last arriver (low byte 4) both that the round is complete and whether any
@@ -1525,29 +1418,18 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
 // snap_init_sources / sssp_init_sources, before the group barrier.)
 // The fences stay local-only around relaxed atomics (an acquire / release atomic would add vmcnt(0)).
 // h / w / pitch / direction and the source's src_ok are made uniform once, not per round.
-#ifdef GS_SPEC_ROOM
-// (the room-class instances: RH x RW the class's room and DIR the wave's direction, both compile-time,
-// so sweep()'s switch, its sweep_asm<DIR, CPL, 95> choice, len / span / fwd, the mask addresses and
-// the bits64 bounds fold; -1 / 0: the run-time values, as S1 / S2 take them)
+// (GS_SPEC_ROOM, the room-class instances: RH x RW the class's room and DIR the wave's direction, both
+// compile-time, so sweep()'s switch, its sweep_asm<DIR, CPL, 95> choice, len / span / fwd, the mask
+// addresses and the bits64 bounds fold; -1 / 0: the run-time values, as S1 / S2 take them)
 template <int DIR = -1, int RH = 0, int RW = 0>
-#endif
 __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
 {
-    static_assert(!SSSP_CHECK, "the fixpoint-check build keeps sssp_rounds (simaps_spec.hip)");
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef GS_SPEC_ROOM
     const int h = RH ? RH : __builtin_amdgcn_readfirstlane(sh.h), w = RW ? RW : __builtin_amdgcn_readfirstlane(sh.w);
-#else
-    const int h = __builtin_amdgcn_readfirstlane(sh.h), w = __builtin_amdgcn_readfirstlane(sh.w);
-#endif
     const int pw = sssp_pitch(w);
     const int max_rounds = h * w + 16;  // a converged round changes nothing; the cap guards a bug
     const int s = wave >> 2;
-#ifdef GS_SPEC_ROOM
     const int dir = DIR >= 0 ? DIR : (wave + 2 * s) & 3;
-#else
-    const int dir = (wave + 2 * s) & 3;
-#endif
     const bool ok = __builtin_amdgcn_readfirstlane(sh.src_ok[s]) != 0;
     unsigned *word = reinterpret_cast<unsigned *>(sh.changed[s]);
     unsigned *tmo = &sh.bar[2 + s][2];
@@ -1565,7 +1447,7 @@ __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
         if (round == 0) STAMP_NB(32 + wave);
         if (round == 0 && wave == 0) STAMP_CLK(44);
         unsigned long long bclk[2] = {0, 0};
-        const bool imp = ok && sweep(D, h, w, pw, dir, sh.dirty[s], steps, 0, 1, SSSP_INLINE_MARKS, bclk);
+        const bool imp = ok && sweep(D, h, w, pw, dir, sh.dirty[s], steps, 0, 1, bclk);
         ROUND_BOUNDARY_STAMP(sh, s, round, bclk, bend);
         if (round == 0 && wave == 0) STAMP_NB(22);
         if (round == 0 && wave == 2) STAMP_NB(23);
@@ -1612,15 +1494,12 @@ __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
         }
     }
 }
-#endif
 
-#ifdef GS_SPEC_ROOM
-// A room-class instance's rounds: each sweep wave branches once, on its wave-uniform direction, into
-// the rounds loop instantiated for it.  (SIMAPS_SPEC_NO_DIR_ROUNDS: the room fixed, the direction not.)
+// GS_SPEC_ROOM / GS_SPEC_DIR_ROUNDS: a room-class instance's rounds -- each sweep wave branches once, on
+// its wave-uniform direction, into the rounds loop instantiated for it.
 template <int RH, int RW>
 __device__ __forceinline__ void sssp_rounds_room(Shared &sh, float *dist)
 {
-#ifdef GS_SPEC_DIR_ROUNDS
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     switch ((wave + 2 * (wave >> 2)) & 3) {  // sssp_rounds_word's own dir
     case 0: sssp_rounds_word<0, RH, RW>(sh, dist); break;
@@ -1628,14 +1507,9 @@ __device__ __forceinline__ void sssp_rounds_room(Shared &sh, float *dist)
     case 2: sssp_rounds_word<2, RH, RW>(sh, dist); break;
     default: sssp_rounds_word<3, RH, RW>(sh, dist); break;
     }
-#else
-    sssp_rounds_word<-1, RH, RW>(sh, dist);
-#endif
 }
-#endif
 
-#ifdef GS_SPEC_FUSED_SNAP  // (simaps_spec.hip: the compile-time instances of get_state_kernel only)
-// snap_sources + sssp_init_sources with one group barrier instead of two where every query pixel is
+// GS_SPEC_FUSED_SNAP: snap_sources + sssp_init_sources with one group barrier instead of two where every query pixel is
 // free (the common case): a free query pixel is its own snapped source, so each thread that needs a
 // source's cell tests the pixel itself and writes the source's distance 0 / its dirty line at once.
 // A pixel that is not free takes snap_sources' EDT path and sssp_init_sources as they are.
@@ -1704,13 +1578,12 @@ __device__ __forceinline__ void sssp_rounds(Shared &sh, float *dist, int nsrc, c
         // waves go to SIMD (wave % 4): source 1's directions are rotated by 2 so that every SIMD
         // hosts one row sweep and one column sweep (the long ones would otherwise share two SIMDs)
 #ifdef SIMAPS_PHASE_STAMPS
-        if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps, 0, 1,
-                                  SSSP_INLINE_MARKS, bclk) && (tid & 63) == 0 && !SSSP_CHECK)
+        if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps, 0, 1, bclk) &&
+            (tid & 63) == 0)
             changed[round % 3] = 1;
         ROUND_BOUNDARY_STAMP(sh, s, round, bclk, bend);
 #else
-        if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps) && (tid & 63) == 0 &&
-            !SSSP_CHECK)
+        if (sh.src_ok[s] && sweep(dist + s * DIST_FLOATS, h, w, pw, (wave + 2 * s) & 3, sh.dirty[s], steps) && (tid & 63) == 0)
             changed[round % 3] = 1;
 #endif
 #ifdef SIMAPS_PHASE_STAMPS
@@ -1720,21 +1593,6 @@ __device__ __forceinline__ void sssp_rounds(Shared &sh, float *dist, int nsrc, c
         if (round == 0 && wave == 0) STAMP_CLK(45);
 #endif
         gs.sync();
-        if (SSSP_CHECK) {  // every edge; the violated ones mark the next round's lines
-#ifdef SIMAPS_PHASE_STAMPS
-            if (tid == 0 && round == 0) STAMP_NB(56);
-#endif
-            if (sh.src_ok[s] && sssp_check(dist + s * DIST_FLOATS, h, w, pw, sh.dirty[s], tid & 255, 256) && (tid & 63) == 0)
-                changed[round % 3] = 1;
-#ifdef SIMAPS_PHASE_STAMPS
-            if (tid == 0 && round == 0) STAMP_NB(57);
-            if (tid == 192 && round == 0) STAMP_NB(63);
-#endif
-            gs.sync();
-#ifdef SIMAPS_PHASE_STAMPS
-            if (tid == 0 && round == 0) STAMP_NB(78);
-#endif
-        }
         if (!changed[round % 3] || round >= max_rounds) {
             if ((tid & 255) == 0)  // cap hit: 1 << 20 (status bit 1)
                 __hip_atomic_fetch_max(&sh.rounds, round >= max_rounds ? 1 << 20 : round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1817,16 +1675,11 @@ __device__ __forceinline__ void sssp_max(Shared &sh, const float *dist, int nsrc
 // Split sweeps (one source, compile-time pitch; the single-kernel users, whose other waves idle): the
 // two directions along the longer room side get KL waves each, the other two KS each, every wave one
 // part of its direction's steps (sweep(..., part, nparts)).  Shorter sweeps per round, more rounds.
-// Measured (tools/sssp_split_ab.sh, profiles/r3g_sssp_split_ab.jsonl): KL = KS = 2 takes 2-7 % off
+// Measured in round 3 (profiles/archive/r3g_sssp_split_ab.jsonl): KL = KS = 2 takes 2-7 % off
 // simaps_sssp_grid and simaps_sp_distance; KL = 2 alone, 3 alone, or 4 / 2 are slower than no split
 // (their extra rounds outweigh the shorter ones).
-#ifndef SIMAPS_SSSP_SPLIT_L
-#define SIMAPS_SSSP_SPLIT_L 2
-#endif
-#ifndef SIMAPS_SSSP_SPLIT_S
-#define SIMAPS_SSSP_SPLIT_S 2
-#endif
-constexpr int SPLIT_WAVES = 2 * (SIMAPS_SSSP_SPLIT_L + SIMAPS_SSSP_SPLIT_S);
+constexpr int SPLIT_L = 2, SPLIT_S = 2;  // KL, KS
+constexpr int SPLIT_WAVES = 2 * (SPLIT_L + SPLIT_S);
 static_assert(SPLIT_WAVES <= NT / 64, "split sweeps: one wave per part");
 __device__ __forceinline__ void sssp_rounds_split(Shared &sh, float *dist)
 {
@@ -1835,24 +1688,19 @@ __device__ __forceinline__ void sssp_rounds_split(Shared &sh, float *dist)
     const int max_rounds = h * w + 16;
     const Group gs{tid, 64 * SPLIT_WAVES, sh.bar[2], SPLIT_WAVES};
     const int longd = w >= h ? 2 : 0;  // columns (right / left) sweep the w lines of a wide room
-    const bool lw = wave < 2 * SIMAPS_SSSP_SPLIT_L;
-    const int q = lw ? wave : wave - 2 * SIMAPS_SSSP_SPLIT_L;
+    const bool lw = wave < 2 * SPLIT_L;
+    const int q = lw ? wave : wave - 2 * SPLIT_L;
     const int dir = (lw ? longd : 2 - longd) + (q & 1), part = q >> 1;
-    const int nparts = lw ? SIMAPS_SSSP_SPLIT_L : SIMAPS_SSSP_SPLIT_S;
+    const int nparts = lw ? SPLIT_L : SPLIT_S;
     if (lw) __builtin_amdgcn_s_setprio(3);
     else __builtin_amdgcn_s_setprio(2);
     int *changed = sh.changed[0];
     int steps = 0;
     for (int round = 0;; round++) {
         if (tid == 0) changed[(round + 1) % 3] = 0;
-        if (sh.src_ok[0] && sweep(dist, h, w, pw, dir, sh.dirty[0], steps, part, nparts) && (tid & 63) == 0 && !SSSP_CHECK)
+        if (sh.src_ok[0] && sweep(dist, h, w, pw, dir, sh.dirty[0], steps, part, nparts) && (tid & 63) == 0)
             changed[round % 3] = 1;
         gs.sync();
-        if (SSSP_CHECK) {
-            if (sh.src_ok[0] && sssp_check(dist, h, w, pw, sh.dirty[0], tid, 64 * SPLIT_WAVES) && (tid & 63) == 0)
-                changed[round % 3] = 1;
-            gs.sync();
-        }
         if (!changed[round % 3] || round >= max_rounds) {
             if (tid == 0)
                 __hip_atomic_fetch_max(&sh.rounds, round >= max_rounds ? 1 << 20 : round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2099,7 +1947,7 @@ __device__ __forceinline__ void wait_scratch(Shared &sh)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-#ifdef GS_SPEC_EARLY_ZERO  // (simaps_spec.hip: the two-source compile-time instance of get_state_kernel only)
+#ifdef GS_SPEC  // GS_SPEC_EARLY_ZERO (simaps_spec.hip: the two-source compile-time instance of get_state_kernel only)
 // One render wave, ahead of the render group's barrier after the robot stamps: if the sweep track has
 // released its scratch (one relaxed load, the local acquire fence), zero this wave's share of the
 // tile's first SCRATCH_Q 16-byte words; otherwise raise the late flag bar[1][3] (zero since the
@@ -2381,7 +2229,7 @@ __device__ __forceinline__ void render_maps(const RenderCtx &rc, const Group &g,
         // early_tile: the code map lies outside the tile and the sweep track zeroed the tile when it
         // released its scratch -- no barrier; else every render wave must be done with the code map
         if (!early_tile) g.sync();
-#ifdef GS_SPEC_EARLY_ZERO
+#ifdef GS_SPEC  // GS_SPEC_EARLY_ZERO
         // (zero_scratch_early: every render wave found the scratch released before the barrier after
         // the stamps and zeroed its share there -- nothing to wait for, no zeroing, no barrier)
         const bool zero_late = __builtin_amdgcn_readfirstlane(
@@ -2391,7 +2239,7 @@ __device__ __forceinline__ void render_maps(const RenderCtx &rc, const Group &g,
 #endif
         if (zero_late || !early_tile || !(cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map))
             wait_scratch(sh);
-#ifdef GS_SPEC_RENDER_ZERO
+#ifdef GS_SPEC  // GS_SPEC_RENDER_ZERO
         // (the two-source instance's sweep track releases its scratch as it is: the tile's first
         // SCRATCH_Q 16-byte words are zeroed here; the rest was zeroed in the params phase.  With one
         // source the 12 render waves are the longer track and the sweep track keeps the zeroing.)
@@ -2615,7 +2463,7 @@ __device__ __forceinline__ void dump_dist(const Shared &sh, const float *dist, f
 // cspace (OccupancyMap.update, envs.py:2453-2454) -> snapped sources (envs.py:2514-2517, 2523-2524)
 // -> distance arrays; then the cspace scratch is released to the render group's raster tile and
 // the sweeps run to the fixpoint (GridGraph._spfa, pyx:69-114), finish and scale in place.
-#ifdef GS_SPEC_ROOM  // (simaps_spec.hip: RH x RW the room of a room-class instance, 0 where it is a run-time value)
+#ifdef GS_SPEC  // GS_SPEC_ROOM (simaps_spec.hip: RH x RW the room of a room-class instance, 0 where it is a run-time value)
 template <int G, int RH = 0, int RW = 0>
 #else
 template <int G>
@@ -2661,7 +2509,7 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
     if (dbg.cspace) {
         for (int k = t; k < h * w; k += g.n) dbg.cspace[(size_t)n * h * w + k] = b_test(S.freeb[k / w], k % w) ? 1 : 0;
     }
-#ifdef GS_SPEC_FUSED_SNAP
+#ifdef GS_SPEC  // GS_SPEC_FUSED_SNAP
     if (nsrc > 0) {
         snap_init_sources(sh, S, dist, nsrc, g);
         if (t == 0) STAMP_NB(48);
@@ -2675,7 +2523,7 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
 #endif
     // every read of the cspace scratch is done (snap_sources ended with a group sync): the render
     // group may now overwrite it with its raster tile -- zeroed here first when early_tile
-#ifdef GS_SPEC_RENDER_ZERO  // (simaps_spec.hip, two sources: the render waves, which have the slack, zero it: render_maps)
+#ifdef GS_SPEC  // GS_SPEC_RENDER_ZERO (simaps_spec.hip, two sources: the render waves, which have the slack, zero it: render_maps)
     if (cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map) zero_tile = false;
 #endif
     if (zero_tile) {
@@ -2689,11 +2537,9 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
         STAMP_NB(3);
     }
     if (nsrc == 0) return;
-#if defined(GS_SPEC_ROOM)
+#ifdef GS_SPEC  // GS_SPEC_ROUND_WORD, and GS_SPEC_ROOM / GS_SPEC_DIR_ROUNDS in the room-class instances
     if constexpr (RH != 0) sssp_rounds_room<RH, RW>(sh, dist);
     else sssp_rounds_word(sh, dist);
-#elif defined(GS_SPEC_ROUND_WORD)
-    sssp_rounds_word(sh, dist);
 #else
     sssp_rounds(sh, dist, nsrc, g);
 #endif
@@ -2730,14 +2576,7 @@ __device__ __forceinline__ void sweep_track(Shared &sh, SsspScratch &S, float *d
 }
 
 #ifndef SIMAPS_DEVICE_ONLY  // (simaps_mixed.hip includes this file for its device helpers only)
-#ifdef SIMAPS_VGPR_CAP  // timing-only A/B build (tools/coresidency_model.py): the kernel squeezed to 8 waves
-                        // per SIMD (<= 64 VGPRs, spills included) -- what two co-resident 16-wave stacks per
-                        // CU would need; its LDS is dynamic so that the occupancy target is honoured
-#define SIMAPS_GS_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))
-#else
-#define SIMAPS_GS_ATTR
-#endif
-__global__ void __launch_bounds__(NT) SIMAPS_GS_ATTR get_state_kernel(
+__global__ void __launch_bounds__(NT) get_state_kernel(
     simaps_config cfg, Geometry geo, const simaps_agent *__restrict__ agents, const simaps_env *__restrict__ envs,
     const simaps_robot *__restrict__ robots, const double *__restrict__ paths, const uint8_t *__restrict__ occupancy,
     const float *__restrict__ overhead, float *__restrict__ state, int C, simaps_debug dbg, unsigned *fault)
@@ -3095,9 +2934,6 @@ __device__ __forceinline__ bool line_free(const SH &sh, const SsspScratch &S, in
 #ifndef SIMAPS_POP_CAP  // the diagnostic build (tests/test_gpu_faults.py) lowers it to exercise the fault path
 #define SIMAPS_POP_CAP (1 << 24)
 #endif
-#ifndef SIMAPS_SPFA_PIPE  // the round-4 software-pipelined pop (0: the round-3 pop, for A/B builds)
-#define SIMAPS_SPFA_PIPE 1
-#endif
 #ifndef SIMAPS_SPFA_RING  // > 0: the diagnostic ring build (tests/test_gpu_faults.py) -- a queue ring of at most
 #define SIMAPS_SPFA_RING 0  // this many slots, so that the ring wraps many times per query (the product's
 #endif                      // ring has one slot per cell and rarely wraps); a live queue past it is a fault
@@ -3148,9 +2984,6 @@ __device__ __forceinline__ int dir_off(int k, int pw)
     return di * pw + dj;
 }
 
-#ifndef SIMAPS_SPFA_ASM  // the common pops as one inline-asm loop (0: the C++ pop alone, for A/B builds)
-#define SIMAPS_SPFA_ASM 1
-#endif
 // The common SPFA pop (shortest_paths.pyx:89-107) as one inline-asm loop (round 4).  The C++ pop in
 // path_core costs ~85 instructions with the compiler's exec juggling and register copies; this one
 // ~43 (two pops per iteration, so the next second needs no copy).  The next pop's LDS reads are
@@ -3421,12 +3254,8 @@ __device__ __forceinline__ int path_core(PathHdr &sh, SsspScratch &S, char *arr,
         int steps = 0, round = 0;
         for (;; round++) {
             if (tid == 0) sh.changed[(round + 1) % 3] = 0;
-            if (sweep(dist, h, w, pw, wave, sh.dirty, steps) && lane == 0 && !SSSP_CHECK) sh.changed[round % 3] = 1;
+            if (sweep(dist, h, w, pw, wave, sh.dirty, steps) && lane == 0) sh.changed[round % 3] = 1;
             lds_barrier();
-            if (SSSP_CHECK) {
-                if (sssp_check(dist, h, w, pw, sh.dirty, tid, PNT) && lane == 0) sh.changed[round % 3] = 1;
-                lds_barrier();
-            }
             if (!sh.changed[round % 3] || round >= h * w + 16) break;
         }
         if (tid == 0 && round >= h * w + 16) fault_or(sh.fault, SIMAPS_FAULT_ROUNDS);
@@ -3471,7 +3300,6 @@ __device__ __forceinline__ int path_core(PathHdr &sh, SsspScratch &S, char *arr,
         // an unreachable target (fixpoint +inf) never gets a parent: the SPFA cannot change the path
         // (likewise a blocked target, fixpoint -inf: grid paths; movement-path targets are snapped)
         if (EARLY && !OVL && (finT == INFINITY || finT == -INFINITY)) count = 0, early = true;
-#if SIMAPS_SPFA_PIPE
         // the reads of the next pop, issued one pop ahead: its vertex's 8 edge heads and itself
         // (lane 8), the distance of the entry after it (the SLF front during that pop) and the slot
         // after that one
@@ -3488,14 +3316,12 @@ __device__ __forceinline__ int path_core(PathHdr &sh, SsspScratch &S, char *arr,
         // the asm pop addresses the LDS arrays by their compile-time offsets in the kernel's LDS block
         const bool asm_ok = (uint32_t)(uintptr_t)Ld == (uint32_t)OFF_PA && (uint32_t)(uintptr_t)Lq == (uint32_t)(OFF_PA + 4 * CELLS) &&
                             (uint32_t)(uintptr_t)Li == (uint32_t)(OFF_PA + 6 * CELLS);
-#endif
         // pop rounds (inner loop: one exit, so the common pop ends in one compare) up to `lim`, then
         // (EARLY) an early-exit check
         if (count > 0)
             for (;;) {
                 int left = lim - pops;  // pops of this round (the common pop's one exit test: min(count, left))
                 for (;;) {
-#if SIMAPS_SPFA_PIPE && SIMAPS_SPFA_ASM
                     if (asm_ok) {  // the common pops in one asm loop; it returns at `left` = 0 or an uncommon pop
                         int fs = __builtin_amdgcn_readfirstlane(front), ss = __builtin_amdgcn_readfirstlane(second);
                         int ladd = 0;
@@ -3508,9 +3334,6 @@ __device__ __forceinline__ int path_core(PathHdr &sh, SsspScratch &S, char *arr,
                         second = ss;
                         if (left <= 0) break;
                     }
-#endif
-#if SIMAPS_SPFA_PIPE
-                    {
                     // The pop, software-pipelined (round 4).  Its LDS reads -- the popped vertex's 8 edge
                     // heads and itself, the next front's distance, the slot after it -- were issued at the
                     // end of the previous pop, right after that pop's writes, so their latency overlaps
@@ -3604,124 +3427,6 @@ __device__ __forceinline__ int path_core(PathHdr &sh, SsspScratch &S, char *arr,
                     if constexpr (SIMAPS_SPFA_RING > 0)
                         if (count > ring && lane == 0) fault_or(sh.fault, SIMAPS_FAULT_ROUNDS);  // (diagnostic ring overflowed)
                     if (min(count, left) <= 0) break;
-                    continue;
-                    }
-#endif
-                    // (front / second are wave-uniform: keep them in SGPRs across the loop)
-                    const int u = __builtin_amdgcn_readfirstlane(front);
-                    qh = qn;
-                    count--;                           // entries queue[qh .. qt) after the pop
-                    const int F0 = __builtin_amdgcn_readfirstlane(second);  // the next front (valid if count >= 1)
-                    const int q2 = qh + 1 == ring ? 0 : qh + 1;
-                    qn = q2;
-                    const int v = u + doff;
-                    // one round of reads (in-order LDS sees this wave's earlier writes); the ballots below
-                    // consume them together.  Lane 8's v is u: its pin read is u's (parent bits to keep)
-                    // and its distance read is u's (no separate read of dist[u]).
-                    const float dv = Ld[v];
-                    const float du = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), 8));
-                    const int pv = Li[v];
-                    // the front's distance before this pop's relaxations (F0 is a ring slot's content, a cell
-                    // index, always: unused when count == 0)
-                    const float dF0 = Ld[F0];
-                    const int third = Lq[q2];          // queue[qh + 1]: the next pop's second (if count >= 2)
-                    const float nd = du + wl;
-                    // (lanes >= 8: v = u, so nd = du + 1 > dv: never `better`; no lane test needed)
-                    const bool better = nd < dv;
-                    const uint64_t imp = __builtin_amdgcn_ballot_w64(better);
-                    // not queued: bit 4 clear, i.e. pv < 16 (a pin byte is at most 0x18: one compare)
-                    const uint64_t notq = __builtin_amdgcn_ballot_w64(pv < 16);
-                    Li[u] = (uint8_t)(__builtin_amdgcn_readlane(pv, 8) & 0xf);  // u leaves the queue (pyx:92)
-                    int nf = F0, nsecond = __builtin_amdgcn_readfirstlane(third);
-                    if (imp) {
-                        if (better) { Ld[v] = nd; Li[v] = pbits; }
-                        const uint64_t push = imp & notq;
-                        if (push) {
-                            // The pushes of this pop, in edge order (pyx:104-111): each goes to the tail and
-                            // swaps with the front if its distance is below the front's at that moment.  The
-                            // front's distance seen by edge k is F0's, lowered by this pop only if F0 is the
-                            // head of an earlier edge jf < k (F0 is queued, so never pushed, but it may be
-                            // relaxed) -- until the first push that beats it (js); from then on it is the
-                            // running minimum of the pushed distances from js on.  A swapping push's slot
-                            // receives the previous front (F0 or the previous swapping push's vertex); the last
-                            // swapper ends at the front.
-                            const int np = __popcll(push);
-                            // F0 as the head of an edge this pop IMPROVED (lane jf): only then does its
-                            // distance change for the later edges.  (Lanes >= 8 have v = u != F0 and never
-                            // improve; with an empty queue F0 is stale, but that case ignores jf.)
-                            const uint64_t fmi = __builtin_amdgcn_ballot_w64(v == F0) & imp;
-                            const int jf = fmi ? __builtin_ctzll(fmi) : 64;
-                            const float dafter = fmi ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nd), jf)) : dF0;
-                            if (np == 1 && count > 0) {
-                                // one push (the common case): a scalar decision, no scans
-                                const int p1 = __builtin_ctzll(push);
-                                const int vp = __builtin_amdgcn_readlane(v, p1);
-                                const float ndp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nd), p1));
-                                const bool sw = ndp < (p1 > jf ? dafter : dF0);
-                                const int content = sw ? F0 : vp;
-                                Lq[qt] = (uint16_t)content;
-                                if (sw) { Lq[qh] = (uint16_t)vp; nf = vp; }
-                                if (count == 1) nsecond = content;  // the tail slot was queue[qh + 1]
-                                qt = qt + 1 == ring ? 0 : qt + 1;
-                                count++;
-                            } else {
-                                const bool isP = (push >> lane) & 1;
-                                const int rank = __popcll(push & ((1ull << lane) - 1));
-                                uint64_t cand = push;
-                                int Fq = F0;
-                                float dbefore = dF0, dseen = dafter;
-                                if (count == 0) {  // the queue was empty: the first push becomes the front
-                                    const int p1 = __builtin_ctzll(push);
-                                    Fq = __builtin_amdgcn_readlane(v, p1);
-                                    dbefore = dseen = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nd), p1));
-                                    cand &= cand - 1;
-                                }
-                                const bool isC = (cand >> lane) & 1;
-                                const uint64_t sF0 = __ballot(isC && nd < (lane > jf ? dseen : dbefore));
-                                int content = v, newfront = Fq;
-                                if (sF0) {
-                                    const int js = __builtin_ctzll(sF0);
-                                    // exclusive prefix minimum of nd over the candidate lanes in [js, lane) (DPP
-                                    // row shifts: lanes 0-7 lie in one row)
-                                    float y = (isC && lane >= js) ? nd : INFINITY;
-        #define SPFA_SHR(x, n, old) __builtin_amdgcn_update_dpp((old), (x), 0x110 + (n), 0xf, 0xf, false)
-        #define SPFA_SHRF(x, n) __int_as_float(SPFA_SHR(__float_as_int(x), n, (int)INF_BITS))
-                                    y = fminf(y, SPFA_SHRF(y, 1));
-                                    y = fminf(y, SPFA_SHRF(y, 2));
-                                    y = fminf(y, SPFA_SHRF(y, 4));
-                                    const float pm = SPFA_SHRF(y, 1);
-                                    const bool sw = isC && (lane == js || (lane > js && nd < pm));
-                                    const uint64_t swm = __ballot(sw);
-                                    // the previous swapper's vertex: exclusive "last valid" scan of v over swappers
-                                    int z = sw ? v : -1, zs;
-                                    zs = SPFA_SHR(z, 1, -1); z = z >= 0 ? z : zs;
-                                    zs = SPFA_SHR(z, 2, -1); z = z >= 0 ? z : zs;
-                                    zs = SPFA_SHR(z, 4, -1); z = z >= 0 ? z : zs;
-                                    const int prev = SPFA_SHR(z, 1, -1);
-        #undef SPFA_SHRF
-        #undef SPFA_SHR
-                                    if (sw) content = prev >= 0 ? prev : Fq;
-                                    newfront = __builtin_amdgcn_readlane(v, 63 - __builtin_clzll(swm));
-                                }
-                                const int slot = qt + rank < ring ? qt + rank : qt + rank - ring;
-                                if (isP) Lq[slot] = (uint16_t)content;
-                                if (sF0) Lq[qh] = (uint16_t)newfront;  // after the lanes' stores (in the empty case qh is p1's slot)
-                                if (count <= 1) {  // the pushes wrote queue[qh + 1]: the next pop's second
-                                    const uint64_t at = __ballot(isP && slot == q2);
-                                    if (at) nsecond = __builtin_amdgcn_readlane(content, __builtin_ctzll(at));
-                                }
-                                qt = qt + np < ring ? qt + np : qt + np - ring;
-                                count += np;
-                                nf = newfront;
-                            }
-                        }
-                    }
-                    front = nf;
-                    second = nsecond;
-                    --left;
-                    if constexpr (SIMAPS_SPFA_RING > 0)
-                        if (count > ring && lane == 0) fault_or(sh.fault, SIMAPS_FAULT_ROUNDS);  // (diagnostic ring overflowed)
-                    if (min(count, left) <= 0) break;  // (count, left >= 0)
                 }
                 pops = lim - left;
                 if (count <= 0 || pops >= SIMAPS_POP_CAP) break;
@@ -4053,14 +3758,8 @@ constexpr int INGEST_MAX_WC = 1024, INGEST_MAX_ROWS = 32;  // camera width; came
 constexpr bool ingest_width_ok(int wc) { return wc >= 1 && wc <= INGEST_MAX_WC && 1 + (INGEST_PTS - 2) / wc < INGEST_MAX_ROWS; }
 constexpr int ingest_min_width(int wc = 1) { return ingest_width_ok(wc) ? wc : ingest_min_width(wc + 1); }
 static_assert(ingest_min_width() == 67, "include/simaps.h documents the camera width range [67, 1024]");
-#ifndef SIMAPS_INGEST_RES_G
-#define SIMAPS_INGEST_RES_G 8
-#endif
-#ifndef SIMAPS_INGEST_RES_ROWS
-#define SIMAPS_INGEST_RES_ROWS 2
-#endif
 // resolve: INGEST_RES_G workgroups per frame, INGEST_RES_ROWS rows in flight per wave
-constexpr int INGEST_RES_WG = 256, INGEST_RES_G = SIMAPS_INGEST_RES_G, INGEST_RES_ROWS = SIMAPS_INGEST_RES_ROWS;
+constexpr int INGEST_RES_WG = 256, INGEST_RES_G = 8, INGEST_RES_ROWS = 2;
 
 // Camera.capture_image's frame (envs.py:1932-1940) in float32: position, principal, up, right.
 __device__ __forceinline__ void camera_frame(const double *P, float *F)
@@ -4692,7 +4391,6 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     simaps_debug d;
     memset(&d, 0, sizeof(d));
     if (dbg) d = *dbg;
-#ifndef SIMAPS_VGPR_CAP
     // the store launches and the 16-bit launches: a compile-time instance where one matches the call
     // (simaps_spec_store.h, simaps_spec_store.inc); dest == nullptr is simaps_get_state_as
     if (dest || state_dtype != SIMAPS_STATE_F32) {
@@ -4711,7 +4409,6 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
             return 0;
         }
     }
-#endif
     if (dest) {  // simaps_get_state_into: one launch of the element type's kernel (simaps_store.inc)
         if (state_dtype == SIMAPS_STATE_F32)
             simaps_store::launch_get_state_into_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
@@ -4734,7 +4431,6 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
         if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_as launch: %s", hipGetErrorString(e));
         return 0;
     }
-#ifndef SIMAPS_VGPR_CAP
     // a compile-time instance of the kernel where one matches the call (simaps_spec.h, simaps_spec.hip)
     const int inst = simaps_spec::instance_of(*cfg, simaps_spec::any_debug(d));
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
@@ -4747,17 +4443,8 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
         if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
         return 0;
     }
-#endif
-#ifdef SIMAPS_VGPR_CAP
-    static const hipError_t lds_ok =
-        hipFuncSetAttribute((const void *)get_state_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (lds_ok != hipSuccess) return fail(SIMAPS_EHIP, "dynamic LDS of the VGPR-cap build");
-    hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), LDS_BYTES, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, (float *)state, C, d, cx.fault_dev);
-#else
     hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geo, agents, envs,
                        robots, paths, occupancy, overhead, (float *)state, C, d, cx.fault_dev);
-#endif
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
     return 0;

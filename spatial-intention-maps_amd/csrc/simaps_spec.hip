@@ -9,8 +9,10 @@
 // into libsimaps.so beside simaps.hip, whose device helpers it includes (SIMAPS_DEVICE_ONLY).
 //
 // With the flags fixed the render track ends about 3 us before the sweep track,
-// so the instances also move work off the sweep track that the generic kernel keeps there (each
-// -DSIMAPS_SPEC_NO_* restores the generic schedule, for A/B timings):
+// so the instances also move work off the sweep track that the generic kernel keeps there.  Each lever
+// below was once a build switch of its own, timed against the generic schedule (DESIGN.md section 5,
+// HISTORY.md) and decided for; they are now one condition, GS_SPEC: "this unit builds instances".
+// The names stay in the comments at the sites they gate in simaps.hip and get_state_body.inc:
 //   GS_SPEC_FUSED_SNAP   one group barrier for snap + SSSP start (snap_init_sources)
 //   GS_SPEC_RENDER_ZERO  with two sources (8 sweep + 8 render waves) the render waves zero the released
 //                        cspace scratch (sweep_track, render_maps); with one source the 12 render waves
@@ -26,25 +28,6 @@
 //   GS_SPEC_EARLY_ZERO   (with GS_SPEC_RENDER_ZERO) the render waves zero the released scratch ahead
 //                        of the barrier after the robot stamps, and the first raster pass starts
 //                        without a barrier of its own (zero_scratch_early; late release: as before)
-#ifndef SIMAPS_SPEC_NO_FUSED_SNAP
-#define GS_SPEC_FUSED_SNAP
-#endif
-// (the SIMAPS_SSSP_CHECK A/B build ends its rounds with the fixpoint check, which only sssp_rounds runs)
-#if !defined(SIMAPS_SPEC_NO_ROUND_WORD) && !defined(SIMAPS_SSSP_CHECK)
-#define GS_SPEC_ROUND_WORD
-#endif
-#ifndef SIMAPS_SPEC_NO_FLAT_MARKS
-#define GS_SPEC_FLAT_MARKS
-#endif
-#ifndef SIMAPS_SPEC_NO_EARLY_OCC
-#define GS_SPEC_EARLY_OCC
-#endif
-#ifndef SIMAPS_SPEC_NO_RENDER_ZERO
-#define GS_SPEC_RENDER_ZERO
-#endif
-#if defined(GS_SPEC_RENDER_ZERO) && !defined(SIMAPS_SPEC_NO_EARLY_ZERO)
-#define GS_SPEC_EARLY_ZERO
-#endif
 // Room-class instances (GS_SPEC_ROOM; spec.h room_class_of): S1 / S2 with the map shape H x W and the
 // room's h x w fixed as well, for the small room of the BASELINE small_* configurations.  Everything
 // derived from them folds: the pitch, len / span / cells per lane of each sweep direction, the cspace
@@ -53,15 +36,10 @@
 // removed: HISTORY.md Appendix I).
 //   GS_SPEC_DIR_ROUNDS   (with GS_SPEC_ROOM) each sweep wave branches once on its direction into a
 //                        rounds loop instantiated for it (sssp_rounds_room / sssp_rounds_word<DIR>)
-// They take the early occupancy loads and the round words as given (no room instances without them).
-#if !defined(SIMAPS_SPEC_NO_ROOM) && defined(GS_SPEC_ROUND_WORD) && defined(GS_SPEC_EARLY_OCC)
-#define GS_SPEC_ROOM
-#ifndef SIMAPS_SPEC_NO_DIR_ROUNDS
-#define GS_SPEC_DIR_ROUNDS
-#endif
+// They take the early occupancy loads and the round words as given.
+#define GS_SPEC  // (GS_ROOM_H x GS_ROOM_W: the kernel's room-class template arguments, for get_state_body.inc)
 #define GS_ROOM_H RH
 #define GS_ROOM_W RW
-#endif
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
 #include "spec.h"
@@ -84,14 +62,12 @@ __global__ void __launch_bounds__(NT) get_state_spec_kernel(
     cfg.use_history_map = 0;
     cfg.use_intention_channels = 0;
     cfg.layout_chw = 1;
-#ifdef GS_SPEC_ROOM
-    if (RH) {
+    if (RH) {  // GS_SPEC_ROOM
         cfg.H = MH;
         cfg.W = MW;
         cfg.room_h = RH;
         cfg.room_w = RW;
     }
-#endif
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #include "get_state_body.inc"
@@ -109,13 +85,11 @@ void launch_get_state(int id, const simaps_config &cfg, const simaps::Geometry &
                       hipStream_t stream)
 {
     spec_kernel_t k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1> : get_state_spec_kernel<0>;
-#ifdef GS_SPEC_ROOM
     // the room-class twin of S1 / S2 where cfg's shape matches a class exactly (spec.h)
     if (room_class_of(cfg) == SIMAPS_ROOM_SMALL) {
         constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
         k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1, MH, MW, RH, RW> : get_state_spec_kernel<0, MH, MW, RH, RW>;
     }
-#endif
     hipLaunchKernelGGL(k, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy, overhead,
                        state, C, fault);
 }
@@ -134,11 +108,7 @@ int simaps_spec_room_abi_version(void) { return SIMAPS_SPEC_ROOM_ABI_VERSION; }
 int simaps_get_state_room_class(const simaps_config *cfg, int has_debug)
 {
     if (!cfg) return SIMAPS_EINVAL;
-#ifdef GS_SPEC_ROOM
     if (simaps_spec::instance_of(*cfg, has_debug != 0) == SIMAPS_SPEC_GENERIC) return SIMAPS_ROOM_NONE;
     return simaps_spec::room_class_of(*cfg);
-#else
-    return SIMAPS_ROOM_NONE;  // (an A/B build without the room instances)
-#endif
 }
 }

@@ -6,7 +6,7 @@
 //
 // The body is get_state_kernel's (get_state_body.inc with GS_MIXED 0) with three things at once:
 //   - the fixed fields of S1 / S2 and of their room-class twins, exactly as get_state_spec_kernel
-//     (simaps_spec.hip) fixes them, under the same GS_SPEC_* levers and -DSIMAPS_SPEC_NO_* switches;
+//     (simaps_spec.hip) fixes them, with the same levers (GS_SPEC);
 //   - SIMAPS_STATE16 for the element type;
 //   - GS_INTO for the store row: get_state_into_kernel's contract (simaps_store.inc) -- dest[blockIdx.x]
 //     is read first, -1 returns before anything is touched, a row outside [0, capacity) posts
@@ -25,33 +25,9 @@
 #if SIMAPS_STORE_DTYPE != 0
 #define SIMAPS_STATE16 SIMAPS_STORE_DTYPE
 #endif
-// ---- the levers of simaps_spec.hip, which documents each
-#ifndef SIMAPS_SPEC_NO_FUSED_SNAP
-#define GS_SPEC_FUSED_SNAP
-#endif
-#if !defined(SIMAPS_SPEC_NO_ROUND_WORD) && !defined(SIMAPS_SSSP_CHECK)
-#define GS_SPEC_ROUND_WORD
-#endif
-#ifndef SIMAPS_SPEC_NO_FLAT_MARKS
-#define GS_SPEC_FLAT_MARKS
-#endif
-#ifndef SIMAPS_SPEC_NO_EARLY_OCC
-#define GS_SPEC_EARLY_OCC
-#endif
-#ifndef SIMAPS_SPEC_NO_RENDER_ZERO
-#define GS_SPEC_RENDER_ZERO
-#endif
-#if defined(GS_SPEC_RENDER_ZERO) && !defined(SIMAPS_SPEC_NO_EARLY_ZERO)
-#define GS_SPEC_EARLY_ZERO
-#endif
-#if !defined(SIMAPS_SPEC_NO_ROOM) && defined(GS_SPEC_ROUND_WORD) && defined(GS_SPEC_EARLY_OCC)
-#define GS_SPEC_ROOM
-#ifndef SIMAPS_SPEC_NO_DIR_ROUNDS
-#define GS_SPEC_DIR_ROUNDS
-#endif
+#define GS_SPEC  // this unit builds instances: the levers of simaps_spec.hip, which documents each
 #define GS_ROOM_H RH
 #define GS_ROOM_W RW
-#endif
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
 #include "spec_store.h"
@@ -106,14 +82,12 @@ __global__ void __launch_bounds__(NT) GSS_KERNEL(
     cfg.use_history_map = 0;
     cfg.use_intention_channels = 0;
     cfg.layout_chw = 1;
-#ifdef GS_SPEC_ROOM
-    if (RH) {
+    if (RH) {  // GS_SPEC_ROOM
         cfg.H = MH;
         cfg.W = MW;
         cfg.room_h = RH;
         cfg.room_w = RW;
     }
-#endif
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #define GS_INTO 1
@@ -138,20 +112,18 @@ void GSS_LAUNCH(int id, const simaps_config &cfg, const simaps::Geometry &geo, i
                 hipStream_t stream)
 {
     spec_store_kernel_t k = id == SIMAPS_SPEC_S1 ? GSS_KERNEL<1> : GSS_KERNEL<0>;
-#ifdef GS_SPEC_ROOM
     // the room-class twin of S1 / S2 where cfg's shape matches a class exactly (spec.h)
     if (simaps_spec::room_class_of(cfg) == SIMAPS_ROOM_SMALL) {
         constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
         k = id == SIMAPS_SPEC_S1 ? GSS_KERNEL<1, MH, MW, RH, RW> : GSS_KERNEL<0, MH, MW, RH, RW>;
     }
-#endif
     hipLaunchKernelGGL(k, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy, overhead,
                        store, capacity, dest, C, fault);
 }
 }  // namespace simaps_spec_store
 
 #if SIMAPS_STORE_DTYPE == 0
-// the queries of include/simaps_spec_store.h (here, where GS_SPEC_ROOM is known)
+// the queries of include/simaps_spec_store.h
 extern "C" {
 int simaps_spec_store_abi_version(void) { return SIMAPS_SPEC_STORE_ABI_VERSION; }
 
@@ -170,13 +142,9 @@ int simaps_get_state_room_class_as(const simaps_config *cfg, int state_dtype, in
 {
     if (!cfg || !spec_store_dtype_ok(state_dtype)) return SIMAPS_EINVAL;
     if (state_dtype == SIMAPS_STATE_F32 && !into) return simaps_get_state_room_class(cfg, has_debug);
-#ifdef GS_SPEC_ROOM
     if (simaps_spec_store::instance_as(*cfg, state_dtype, into != 0, has_debug != 0) == SIMAPS_SPEC_GENERIC)
         return SIMAPS_ROOM_NONE;
     return simaps_spec::room_class_of(*cfg);
-#else
-    return SIMAPS_ROOM_NONE;  // (an A/B build without the room instances)
-#endif
 }
 }
 #endif

@@ -9,24 +9,14 @@
 #include "simaps_spec_store.h"
 #include "spec.h"
 
-// The two families of launches, each dispatched to instances or left with its generic kernel as a
-// whole (DESIGN.md section 5 has the timings that decide it); -DSIMAPS_SPEC_NO_STORE16 restores the
-// generic kernels for both, for A/B timings.
-#ifndef SIMAPS_SPEC_NO_STORE16
-#define SIMAPS_SPEC_STORE_INTO 1   // simaps_get_state_into: float32, bf16, fp16
-#define SIMAPS_SPEC_STORE_PLAIN16 1  // simaps_get_state_as: bf16, fp16
-#else
-#define SIMAPS_SPEC_STORE_INTO 0
-#define SIMAPS_SPEC_STORE_PLAIN16 0
-#endif
-
 namespace simaps_spec_store {
 // The instance (SIMAPS_SPEC_*) that a launch of element type state_dtype takes, `into` a store or
-// not; float32 without a store is simaps_get_state's own choice (spec.h).
-inline int instance_as(const simaps_config &c, int state_dtype, bool into, bool has_debug)
+// not.  Both families of launches -- simaps_get_state_into (float32, bf16, fp16) and simaps_get_state_as
+// (bf16, fp16) -- are dispatched to instances as a whole (DESIGN.md section 5 has the timings that
+// decided it), and float32 without a store is simaps_get_state's own choice (spec.h): the same
+// instance in every case.
+inline int instance_as(const simaps_config &c, int /*state_dtype*/, bool /*into*/, bool has_debug)
 {
-    if (state_dtype == SIMAPS_STATE_F32 && !into) return simaps_spec::instance_of(c, has_debug);
-    if (!(into ? SIMAPS_SPEC_STORE_INTO : SIMAPS_SPEC_STORE_PLAIN16)) return SIMAPS_SPEC_GENERIC;
     return simaps_spec::instance_of(c, has_debug);
 }
 

@@ -176,6 +176,45 @@ def test_library_source_hash_matches_the_tree():
     assert 'include/simaps.h' in rels and 'csrc/simaps.hip' in rels and 'csrc/grid_large.h' in rels
 
 
+def test_build_switches_are_the_makefile_table():
+    """Every SIMAPS_* macro that the device sources test in a preprocessor condition is an ABI constant
+    (defined unconditionally in csrc/ or include/), a unit-mode macro that an including unit sets for
+    itself, or a build switch named in the table at the top of csrc/Makefile -- and the table names no
+    other.  A new experiment's switch has to enter the table, and leave it with its code."""
+    import glob
+    csrc = os.path.join(ROOT, 'spatial-intention-maps_amd', 'csrc')
+    srcs = sorted(f for ext in ('hip', 'h', 'inc') for f in glob.glob(os.path.join(csrc, '*.' + ext)))
+    assert len(srcs) > 30
+    tested, unconditional = set(), set()
+    for path in srcs + sorted(glob.glob(os.path.join(ROOT, 'include', '*.h'))):
+        text = open(path).read().replace('\\\n', ' ')
+        guard = re.search(r'^#ifndef (\w+)\n#define \1\n', text, re.M)  # a header's include guard is no condition
+        open_ifs = []  # the conditions a line stands under, innermost last
+        for line in text.splitlines():
+            code = line.split('//')[0]
+            m = re.match(r'\s*#\s*(\w+)\s*(.*)', code)
+            if m and m.group(1) in ('if', 'ifdef', 'ifndef', 'elif'):
+                if path in srcs:
+                    tested |= set(re.findall(r'\bSIMAPS_\w+', m.group(2)))
+                if m.group(1) != 'elif':
+                    open_ifs.append(bool(guard) and m.group(1) == 'ifndef' and m.group(2).strip() == guard.group(1))
+            elif m and m.group(1) == 'endif':
+                open_ifs.pop()
+            elif m and m.group(1) == 'define' and all(open_ifs):
+                unconditional.add(m.group(2).split('(')[0].split()[0])
+        assert not open_ifs, path
+    unit_mode = {'SIMAPS_DEVICE_ONLY', 'SIMAPS_STATE16', 'SIMAPS_STORE_DTYPE'}
+    switches = tested - unconditional - unit_mode
+    top = []  # the Makefile's leading comment
+    for line in open(os.path.join(csrc, 'Makefile')):
+        if not line.startswith('#'):
+            break
+        top.append(line)
+    table = set(re.findall(r'^#   (SIMAPS_\w+) ', ''.join(top), re.M))
+    assert len(table) >= 8, table
+    assert switches == table, (sorted(switches - table), sorted(table - switches))
+
+
 def test_stale_library_is_refused(tmp_path):
     """A copy of the tree whose kernel source differs from what its libsimaps.so was built from -- here
     only a comment -- refuses to load the library; the unmodified copy loads it."""

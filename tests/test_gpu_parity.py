@@ -314,7 +314,8 @@ def _room_grids(n, h, w, seed):
 @pytest.mark.parametrize('h', [44, 92])
 def test_sssp_grid_room_width_92(S, h):
     """Rooms 92 cells wide (the BASELINE rooms' pitch 95: the sweeps' compile-time asm loops, and the
-    split-sweep variant when built with SIMAPS_SSSP_SPLIT_L / _S), with a divider: bitwise the SPFA."""
+    split sweeps that one-source queries take at that pitch, sssp_rounds_split), with a divider:
+    bitwise the SPFA."""
     batch, K, synthetic = S
     grids, srcs = _room_grids(6, h, 92, 40 + h)
     out = batch.sssp_grid(torch.from_numpy(grids).cuda(), torch.tensor(srcs, dtype=torch.int32),

@@ -13,9 +13,10 @@ measurements:
      plus the grey-dilation cross for the tile), the descriptor / segment block as today.  Feasible
      iff <= 81,920 B.
   2. Registers: the measured cost of the 64-VGPR budget (the kernel built with amdgpu_waves_per_eu(8, 8)
-     and its LDS made dynamic, SIMAPS_VGPR_CAP -- 112 VGPRs and 220 SGPRs spilled, 308 B/lane of
-     scratch): per-stack time X = T(64 VGPR) / T(product), both at one workgroup per CU
-     (profiles/r6f_v64.jsonl vs profiles/r6f_prod.jsonl).
+     and its LDS made dynamic -- 112 VGPRs and 220 SGPRs spilled, 308 B/lane of scratch): per-stack
+     time X = T(64 VGPR) / T(product), both at one workgroup per CU.  That measuring build and its
+     switch have been removed from the sources; its numbers are in profiles/r6f_v64.jsonl (against
+     profiles/r6f_prod.jsonl).
   3. Contention: the co-resident pair shares each SIMD's issue.  Measured for the SSSP sweep step
      (tools/micro/sweep_mb.hip, round 2, HISTORY.md appendix B): 126 cycles with <= 1 sweep wave per
      SIMD, 148 with 2, 291 with 4 -- the CU saturates at 4 sweep waves per SIMD.  Two stacks double the
