@@ -47,6 +47,16 @@
         else cspace_load4<256>(pre4, occ_slot, H, W, cfg.room_i0, cfg.room_j0, cfg.room_h, tid);
     }
 #endif
+#ifdef GS_CACHED  // (simaps_spec_cached.hip: the map slot's cache record -- none for a slot beyond the cache -- whose key
+                  // and window words the sweep waves load beside their occupancy; sc_join: a sweep wave of a hit
+                  // that has left the sweep track for the render track)
+    char *const sc_rec = (unsigned)ag.map_slot < (unsigned)cache_records
+                             ? cache + (size_t)ag.map_slot * simaps_state_cache::record_bytes(GS_ROOM_H, GS_ROOM_W)
+                             : nullptr;
+    CachePre sc_pre;
+    if (pre_occ) cache_preload<GS_ROOM_H, GS_ROOM_W>(sc_pre, sc_rec, tid);
+    bool sc_join = false;
+#endif
     simaps_env ev = envs[ag.env];
     // descriptors come through the C ABI unchecked: clamp what would index past the LDS tables
     // (robot records, segment slots) and report it (SIMAPS_FAULT_DESCRIPTOR)
@@ -86,6 +96,8 @@
         const uint8_t *occ_base = occupancy + ((int64_t)map_off[ag.map_slot] - (int64_t)ag.map_slot * H * W);
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occ_base, nsrc, dbg, n, g, early_tile);
+#elif defined(GS_CACHED)  // (two sources, a room class, the dword loads: the launcher saw to it)
+        sc_join = sweep_track_cached<GS_ROOM_H, GS_ROOM_W>(sh, S, dist, cfg, geo, ag, ev, robots, sc_rec, pre8, sc_pre, g);
 #elif defined(GS_SPEC)  // GS_SPEC_ROOM (simaps_spec.hip: GS_ROOM_H x GS_ROOM_W the instance's compile-time room, 0 in
                        // S1 / S2) and GS_SPEC_EARLY_OCC (a sweep wave: pre_occ is sweep_track's own use4, so the
                        // loads are there when it wants them)
@@ -99,11 +111,23 @@
         if (cs_waves == 8) sweep_track<512>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
         else sweep_track<256>(sh, S, dist, cfg, geo, ag, ev, robots, occupancy, nsrc, dbg, n, g, early_tile);
 #endif
+#ifdef GS_CACHED
+        if (!sc_join) STAMP_NB(7);
+    }
+    if ((tid >> 6) >= cs_waves || sc_join) {
+        // The render group is waves 8-15 until the barrier after the parameters, where a hit's waves 4-7
+        // join it: from there it is waves 4-15 in the one-source instance's thread mapping (nw 12).  A
+        // joining wave has no parameter work: its t lies beyond every parameter thread's until then.
+        int nw = NT / 64 - cs_waves;
+        Group g{tid - 64 * cs_waves, 64 * nw, sh.bar[1], nw};
+        int t = sc_join ? SC_NO_PARAM_THREAD : g.t;
+#else
         STAMP_NB(7);
     } else {
         const int nw = NT / 64 - cs_waves;
         const Group g{tid - 64 * cs_waves, 64 * nw, cs_waves ? sh.bar[1] : nullptr, nw};
         const int t = g.t;
+#endif
         const simaps_robot *rb = robots + ev.robot_off;
         // ---- parameters (one lane per robot; the agent's own local rotation on another wave)
         if (t == 0) {
@@ -158,10 +182,19 @@
             sh.mwin[120 + q] = f == 0 ? geo.mrow0[m] : f == 1 ? geo.mcol0[m] : f == 2 ? geo.mnrows[m] : geo.mncols[m];
         }
         if (t == 0) STAMP_NB(75);
+#ifdef GS_CACHED  // (the sweep group's verdict, waited for if need be: 8 or 12 waves meet at this barrier)
+        if (sc_join || cache_verdict_hit(sh)) {
+            nw = 12;
+            g = Group{tid - 256, 768, sh.bar[1], 12};
+        }
+#endif
         g.sync();
         if (t == 0) STAMP_NB(9);
         if (segs) seg_ramp(sh, t - 320);  // (the segment table is read at raster time, many barriers later)
         if (cfg.use_intention_channels && t == 256) intention_channel_order(sh, cfg, rb);
+#ifdef GS_CACHED
+        t = g.t;
+#endif
 
         if (t == 0) STAMP_NB(51);
         // ---- rotated robot stamps (Mapper._create_global_robot_map, envs.py:2251-2276): each robot's

@@ -55,6 +55,7 @@
 #include "spec.h"
 #include "spec_store.h"
 #include "state16.h"
+#include "state_cache.h"
 #include "store.h"
 
 using namespace simaps;
@@ -592,12 +593,14 @@ __device__ __forceinline__ unsigned row16_or(unsigned x)
 template <int G>
 __device__ __forceinline__ void build_cspace(SsspScratch &S, const OccLoad<G> *L, int h, int w, int r, const Group &g,
                                              float *dist = nullptr, int nsrc = 0, const OccLoad4<G> *L4 = nullptr,
-                                             const uint8_t *occ = nullptr, int H = 0, int W = 0, int i0 = 0, int j0 = 0)
+                                             const uint8_t *occ = nullptr, int H = 0, int W = 0, int i0 = 0, int j0 = 0,
+                                             bool have_win = false)
 {
     const int t = g.t, lane = t & 63, wave = t >> 6;
     const int whM = h + 2 * RMAX, wwM = w + 2 * RMAX;
     const int sub = L4 ? L4->sub : 0;  // window bit k = column k - sub (dword loads)
-    if (L4) {
+    if (have_win) {  // (simaps_spec_cached.hip: the group has built S.win itself and synchronised)
+    } else if (L4) {
         win_from_dwords<G>(S, *L4, whM, t);
     } else if (!L) {
         win_from_bytes<G>(S, occ, H, W, i0, j0, h, w, t);
@@ -622,7 +625,7 @@ __device__ __forceinline__ void build_cspace(SsspScratch &S, const OccLoad<G> *L
             if (lane < 8 && rb + lane < whM) S.win[rb + lane][2] = (m >> (8 * lane)) & 0xffu;
         }
     }
-    g.sync();
+    if (!have_win) g.sync();
     if (t == 0) STAMP_NB(15);
     const B128 fm = b_mask(w);
     const int ln = t & 63;
@@ -1421,14 +1424,15 @@ __device__ __forceinline__ void sssp_init_sources(Shared &sh, float *dist, int n
 // (GS_SPEC_ROOM, the room-class instances: RH x RW the class's room and DIR the wave's direction, both
 // compile-time, so sweep()'s switch, its sweep_asm<DIR, CPL, 95> choice, len / span / fwd, the mask
 // addresses and the bits64 bounds fold; -1 / 0: the run-time values, as S1 / S2 take them)
-template <int DIR = -1, int RH = 0, int RW = 0>
+// (SWAP 1, simaps_spec_cached.hip: source 1 on waves 0-3 and source 0 on waves 4-7)
+template <int DIR = -1, int RH = 0, int RW = 0, int SWAP = 0>
 __device__ __forceinline__ void sssp_rounds_word(Shared &sh, float *dist)
 {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = RH ? RH : __builtin_amdgcn_readfirstlane(sh.h), w = RW ? RW : __builtin_amdgcn_readfirstlane(sh.w);
     const int pw = sssp_pitch(w);
     const int max_rounds = h * w + 16;  // a converged round changes nothing; the cap guards a bug
-    const int s = wave >> 2;
+    const int s = (wave >> 2) ^ SWAP;
     const int dir = DIR >= 0 ? DIR : (wave + 2 * s) & 3;
     const bool ok = __builtin_amdgcn_readfirstlane(sh.src_ok[s]) != 0;
     unsigned *word = reinterpret_cast<unsigned *>(sh.changed[s]);
@@ -3932,7 +3936,9 @@ thread_local char g_err[512] = "";
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
 // Diagnostic builds only: the instance (simaps_spec.h) that the last float32 get_state launch took;
 // its translation unit holds the stamp table that simaps_debug_read_stamps then reads.
+// (STAMP_INSTANCE_CACHED: the instance of simaps_state_cache.h, simaps_spec_cached.hip)
 int g_stamp_instance = SIMAPS_SPEC_GENERIC;
+constexpr int STAMP_INSTANCE_CACHED = -1;
 #endif
 
 int fail(int code, const char *fmt, ...)
@@ -4269,6 +4275,7 @@ const char *simaps_source_hash(void) { return SIMAPS_SOURCE_HASH; }
 // Diagnostic build only: copy the stamp table (uint64 [8192][NSTAMP]) to host memory.
 int simaps_debug_read_stamps(unsigned long long *host_out)
 {
+    if (g_stamp_instance == STAMP_INSTANCE_CACHED) return simaps_state_cache::read_stamps(host_out);
     if (g_stamp_instance != SIMAPS_SPEC_GENERIC) return simaps_spec::read_stamps(host_out);
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : SIMAPS_EHIP;
 }
@@ -4370,8 +4377,9 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
                           const simaps_env *envs,
                      const simaps_robot *robots, const double *paths, const uint8_t *occupancy, const float *overhead,
                      void *state, int state_dtype, int num_robots_per_env, const simaps_debug *dbg, void *stream,
-                     const int64_t *dest = nullptr, int64_t capacity = 0)
+                     const int64_t *dest = nullptr, int64_t capacity = 0, void *cache = nullptr, int cache_records = 0)
 {
+    // cache != nullptr: simaps_get_state_cached (simaps_state_cache.h), float32 and no store
     // dest != nullptr: simaps_get_state_into (simaps_store.h) -- `state` is the caller's store of
     // `capacity` stacks (NULL allowed with capacity 0: check_state_into) and dest[n] agent n's row
     int rc = check_cfg(cfg);
@@ -4433,6 +4441,18 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     }
     // a compile-time instance of the kernel where one matches the call (simaps_spec.h, simaps_spec.hip)
     const int inst = simaps_spec::instance_of(*cfg, simaps_spec::any_debug(d));
+    // the instance that reuses an unchanged map's cspace and receptacle distances, where the call brings
+    // a cache and would take that instance's twin (simaps_state_cache.h, simaps_spec_cached.hip)
+    if (cache && cache_records > 0 && simaps_state_cache::uses_cache(*cfg, simaps_spec::any_debug(d))) {
+#if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
+        g_stamp_instance = STAMP_INSTANCE_CACHED;
+#endif
+        simaps_state_cache::launch_get_state(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
+                                             (float *)state, C, cx.fault_dev, cache, cache_records, (hipStream_t)stream);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_cached launch: %s", hipGetErrorString(e));
+        return 0;
+    }
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
     g_stamp_instance = inst;
 #endif
@@ -5039,6 +5059,46 @@ int simaps_ctx_get_state(simaps_ctx *ctx, const simaps_config *cfg, int N, const
 {
     SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
         SIMAPS_STATE_F32, num_robots_per_env, dbg, stream));
+}
+
+// ---- simaps_state_cache.h
+int simaps_state_cache_abi_version(void) { return SIMAPS_STATE_CACHE_ABI_VERSION; }
+
+int simaps_state_cache_bytes(const simaps_config *cfg)
+{
+    const int rc = check_cfg(cfg);
+    if (rc) return rc;
+    return simaps_state_cache::record_bytes(cfg->room_h, cfg->room_w);
+}
+
+static int check_state_cache(const void *cache, int cache_records)
+{
+    if (cache_records < 0) return fail(SIMAPS_EINVAL, "cache_records %d < 0", cache_records);
+    if (cache && ((uintptr_t)cache & 15u)) return fail(SIMAPS_EINVAL, "cache %p is not aligned to 16 bytes", cache);
+    return 0;
+}
+
+int simaps_get_state_cached(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                            const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                            const float *overhead, float *state, int num_robots_per_env, const simaps_debug *dbg,
+                            void *stream, void *cache, int cache_records)
+{
+    const int rc = check_state_cache(cache, cache_records);
+    if (rc) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, SIMAPS_STATE_F32,
+                          num_robots_per_env, dbg, stream, nullptr, 0, cache, cache_records);
+}
+int simaps_ctx_get_state_cached(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                                const uint8_t *occupancy, const float *overhead, float *state,
+                                int num_robots_per_env, const simaps_debug *dbg, void *stream, void *cache,
+                                int cache_records)
+{
+    const int rc = check_state_cache(cache, cache_records);
+    if (rc) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
+        SIMAPS_STATE_F32, num_robots_per_env, dbg, stream, nullptr, 0, cache, cache_records));
 }
 
 // ---- simaps_state16.h

@@ -1,6 +1,6 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
 include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h, include/simaps_spec_room.h,
-include/simaps_spec_store.h, include/simaps_ingest_seq.h and include/simaps_action_as.h).
+include/simaps_spec_store.h, include/simaps_state_cache.h, include/simaps_ingest_seq.h and include/simaps_action_as.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -143,6 +143,20 @@ ROOM_SMALL_SHAPE = (184, 232, 44, 92)  # SIMAPS_ROOM_SMALL_H / _W / _RH / _RW
 EXPORTED_SPEC_STORE = ('simaps_spec_store_abi_version', 'simaps_get_state_instance_as',
                        'simaps_get_state_room_class_as')
 SPEC_STORE_ABI_VERSION = 1  # SIMAPS_SPEC_STORE_ABI_VERSION
+
+
+# include/simaps_state_cache.h: get_state with a per-map-slot record of what an unchanged map makes (with
+# its context twin)
+EXPORTED_STATE_CACHE = ('simaps_state_cache_abi_version', 'simaps_state_cache_bytes', 'simaps_get_state_cached',
+                        'simaps_ctx_get_state_cached')
+STATE_CACHE_ABI_VERSION = 1  # SIMAPS_STATE_CACHE_ABI_VERSION
+STATE_CACHE_MAGIC = 0x53433031  # SIMAPS_STATE_CACHE_MAGIC
+# simaps_state_cache_header: the head of one record
+STATE_CACHE_HEADER_DTYPE = np.dtype([(n, '<i4') for n in (
+    'magic', 'H', 'W', 'room_i0', 'room_j0', 'room_h', 'room_w', 'cspace_radius', 'has_receptacle', 'rec_i', 'rec_j',
+    'reserved0', 'snap_i', 'snap_j', 'src_ok')] + [('dist_max', '<f4'), ('hits', '<u4'), ('misses', '<u4'),
+                                                    ('reserved1', '<u4', (2,))], align=True)
+assert STATE_CACHE_HEADER_DTYPE.itemsize == 80
 
 
 # include/simaps_ingest_seq.h: several frames per map slot in one launch, applied in order (with its
@@ -296,6 +310,19 @@ def _load(path=LIB_PATH):
         if vs != SPEC_STORE_ABI_VERSION:
             raise ImportError('libsimaps spec_store ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vs, SPEC_STORE_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_cached'):  # (include/simaps_state_cache.h; absent only in an older revision's A/B build)
+        L.simaps_state_cache_abi_version.restype = i32
+        L.simaps_state_cache_bytes.argtypes = [ctypes.POINTER(Config)]
+        L.simaps_state_cache_bytes.restype = i32
+        # simaps_get_state's list with the cache and its record count after stream
+        L.simaps_get_state_cached.argtypes = list(L.simaps_get_state.argtypes) + [vp, i32]
+        L.simaps_get_state_cached.restype = i32
+        L.simaps_ctx_get_state_cached.argtypes = [vp] + list(L.simaps_get_state_cached.argtypes)
+        L.simaps_ctx_get_state_cached.restype = i32
+        vc = L.simaps_state_cache_abi_version()
+        if vc != STATE_CACHE_ABI_VERSION:
+            raise ImportError('libsimaps state_cache ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vc, STATE_CACHE_ABI_VERSION))
     if hasattr(L, 'simaps_ingest_seq'):  # (include/simaps_ingest_seq.h; absent only in an older revision's A/B build)
         L.simaps_ingest_seq_abi_version.restype = i32
         # simaps_ingest's list with seq and num_seq after seg_raw
@@ -347,6 +374,14 @@ class _OldAbi:
 
 
 lib = _load()
+
+
+def has_entry(name, L=None):
+    """Whether the library exports simaps_<name> (an older revision's A/B build may lack a newer header's)."""
+    try:
+        return hasattr(L or lib, 'simaps_' + name)
+    except SimapsError:
+        return False
 
 EXPORTED = ('simaps_abi_version', 'simaps_last_error', 'simaps_fault_status', 'simaps_num_channels',
             'simaps_robot_mask', 'simaps_pack_robots', 'simaps_get_state', 'simaps_sp_distance', 'simaps_shortest_path', 'simaps_ingest', 'simaps_ingest_chunks', 'simaps_path_mode',

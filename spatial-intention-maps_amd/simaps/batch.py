@@ -257,7 +257,7 @@ class StateBatch(_ArrayUpload):
     what a conv policy consumes) or 'hwc' (the reference's (96, 96, C) memory order).  as_hwc() gives
     the reference's index order as a zero-copy view either way."""
 
-    def __init__(self, scenes, agents=None, device='cuda', layout='chw', context=None):
+    def __init__(self, scenes, agents=None, device='cuda', layout='chw', context=None, state_cache=True):
         if not scenes:
             raise ValueError('a StateBatch needs at least one scene')
         s0 = scenes[0]
@@ -300,6 +300,11 @@ class StateBatch(_ArrayUpload):
         # the stream of the last launch that wrote or read the cache: a next one on another stream
         # waits for it (_rec_wait)
         self._rec_stream = None
+        # the state cache (include/simaps_state_cache.h): one record per map slot, allocated (zeroed) by
+        # the first render() that passes it; the library checks each record against the slot's map on
+        # the device, so nothing here tracks versions.  state_cache=False: never passed.
+        self.state_cache = bool(state_cache)
+        self._state_cache = None
 
     def set_descriptors(self, scenes):
         """Upload a new per-step scene descriptor (poses, controller state, paths)."""
@@ -411,13 +416,16 @@ class StateBatch(_ArrayUpload):
         return _lib.lib.simaps_get_state_room_class_as(self.cfg, _lib.state_dtype_id(dtype or torch.float32),
                                                        int(bool(into)), _has_debug(self, debug, into))
 
-    def render(self, out=None, debug=None, stream=None, slots=None, dtype=None):
+    def render(self, out=None, debug=None, stream=None, slots=None, dtype=None, state_cache=None):
         """Launch the fused kernel: the stacks of every agent (or of map slots `slots`, in that
         order) into `out` (allocated if None).  Asynchronous on `stream` (default: the current
         stream); with a side stream, wait for it before reading `out` on another stream.
         The element type is out.dtype -- float32, or bfloat16 / float16: each value rounded to nearest
         even where the kernel stores it, bit for bit render().to(dtype) without the cast pass
-        (simaps_get_state_as); `dtype` chooses it when render() allocates (default float32)."""
+        (simaps_get_state_as); `dtype` chooses it when render() allocates (default float32).
+        A float32 render without debug outputs passes the batch's state cache
+        (simaps_get_state_cached: the same stacks bit for bit, sooner while a slot's map is unchanged);
+        state_cache=False (here, or for the whole batch at construction) is simaps_get_state as before."""
         agents_d, n = (self.agents_d, self.N) if slots is None else self.subset_descriptor(slots)
         if out is None:
             out = self.alloc_state(n, torch.float32 if dtype is None else dtype)
@@ -438,10 +446,18 @@ class StateBatch(_ArrayUpload):
             dbg = _lib.Debug(*(debug[k].data_ptr() if debug.get(k) is not None else None
                                for k in ('cspace', 'sources', 'dist', 'status')), None if rec is None else rec.data_ptr())
         s, cur = launch_stream(self.device, stream)
-        if rec is not None:
+        sc = None
+        if (self.state_cache if state_cache is None else state_cache) and dbg is None and dtype_id == _lib.STATE_F32 \
+                and (slots is None or len(set(int(k) for k in slots)) == n) and _lib.has_entry('get_state_cached'):
+            sc = self._state_cache_records()  # (a launch names each map slot once: repeated slots go without)
+        if rec is not None or sc is not None:
             self._rec_wait(s)
         nrpe = self.num_robots if self.flags['use_intention_channels'] else 0
-        if dtype_id == _lib.STATE_F32:
+        if sc is not None:
+            _lib.check(_lib.call(self.context, 'get_state_cached', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
+                _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
+                _lib.ptr(out), nrpe, None, _lib.stream_handle(s), _lib.ptr(sc), self.N))
+        elif dtype_id == _lib.STATE_F32:
             _lib.check(_lib.call(self.context, 'get_state', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
                 _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
                 _lib.ptr(out), nrpe, None if dbg is None else dbg, _lib.stream_handle(s)))
@@ -449,14 +465,30 @@ class StateBatch(_ArrayUpload):
             _lib.check(_lib.call(self.context, 'get_state_as', self.cfg, n, _lib.ptr(agents_d), _lib.ptr(self.envs_d),
                 _lib.ptr(self.robots_d), _lib.ptr(self.paths_d), _lib.ptr(self.occupancy), _lib.ptr(self.overhead),
                 _lib.ptr(out), dtype_id, nrpe, None if dbg is None else dbg, _lib.stream_handle(s)))
-        hold(s, cur, out, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, self.overhead, rec,
+        hold(s, cur, out, agents_d, self.envs_d, self.robots_d, self.paths_d, self.occupancy, self.overhead, rec, sc,
              *(debug.values() if debug else ()))
-        if rec is not None:
+        if rec is not None or sc is not None:
             self._rec_record(s)
         if rec is not None:  # every rendered slot's receptacle array is now its current map's
             sl = np.arange(self.N) if slots is None else np.asarray(list(slots), dtype=np.int64)
             self._rec_ver[sl] = self._map_ver[sl]
         return out
+
+    def _state_cache_records(self):
+        """The batch's state cache, [N, simaps_state_cache_bytes] uint8, zeroed when first asked for."""
+        if self._state_cache is None:
+            nb = _lib.lib.simaps_state_cache_bytes(self.cfg)
+            _lib.check(min(nb, 0))
+            self._state_cache = torch.zeros((self.N, nb), dtype=torch.uint8, device=self.device)
+        return self._state_cache
+
+    def state_cache_headers(self):
+        """The headers of the state cache's records (one simaps_state_cache_header per map slot, as a
+        numpy record array; key, results, hit / miss counters), None before the first cached render."""
+        if self._state_cache is None:
+            return None
+        n = _lib.STATE_CACHE_HEADER_DTYPE.itemsize
+        return self._state_cache[:, :n].cpu().numpy().copy().view(_lib.STATE_CACHE_HEADER_DTYPE).reshape(-1)
 
     def alloc_store(self, capacity, dtype=torch.float32):
         """A store of `capacity` stacks for render_into(): [capacity, C, 96, 96] (layout 'chw') or

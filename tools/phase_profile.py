@@ -26,16 +26,24 @@ def main():
     ap.add_argument('--envs', type=int, default=64)
     ap.add_argument('--layout', default='chw')
     ap.add_argument('--dump', default=None, help='save the raw per-workgroup stamp table (.npy)')
+    ap.add_argument('--alternate-maps', action='store_true',
+                    help='flip one pixel of every slot\'s occupancy window before each render, so that the stamped render '
+                         'is a state-cache miss (include/simaps_state_cache.h); the pixel, a window corner, changes no stack')
     args = ap.parse_args()
     L = _lib.lib
     L.simaps_debug_read_stamps.argtypes = [ctypes.c_void_p]
     scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
     b = batch.StateBatch(scenes, layout=args.layout)
     out = b.alloc_state()
+    def flip():
+        if args.alternate_maps:
+            b.occupancy[:, b.cfg.room_i0 - 7, b.cfg.room_j0 - 7] ^= 1
     for _ in range(3):
+        flip()
         b.render(out)
     torch.cuda.synchronize()
     st = np.zeros((8192, 80), dtype=np.uint64)
+    flip()
     b.render(out)
     torch.cuda.synchronize()
     assert L.simaps_debug_read_stamps(st.ctypes.data) == 0
