@@ -364,8 +364,10 @@ def robot_mask(robot_type, show_lifted_cube=False):
     return mask
 
 
-def room_mask(shape, room_width, room_length):
-    i0, j0, h, w = K.room_rect(room_width, room_length)
+def room_mask(shape, room_width, room_length, rect=None):
+    """rect: (i0, j0, h, w) in place of the room's own centred rectangle (a scene's 'room_rect':
+    what simaps_config's room_i0 / room_j0 accept at run time)."""
+    i0, j0, h, w = K.room_rect(room_width, room_length) if rect is None else rect
     m = np.zeros(shape, dtype=np.uint8)
     m[i0:i0 + h, j0:j0 + w] = 1
     return m
@@ -392,7 +394,7 @@ class AgentOracle:
 
     # OccupancyMap.update (envs.py:2445-2460), minus the point scatter (occupancy is the input)
     def _update(self):
-        rm = room_mask(self.shape, self.scene['room_width'], self.scene['room_length'])
+        rm = room_mask(self.shape, self.scene['room_width'], self.scene['room_length'], self.scene.get('room_rect'))
         selem = disk(K.cspace_radius_px(self.robot['type']))
         dil = binary_dilation(self.occupancy, selem).astype(np.uint8)
         self.cspace = (1 - np.maximum(1 - rm, dil)).astype(np.uint8)
