@@ -254,6 +254,10 @@
         if (early_tile && cfg.use_shortest_path_to_receptacle_map && cfg.use_shortest_path_map)
             zero_scratch_early(sh, tile, g);
 #endif
+#if defined(GS_CACHED) && !defined(SIMAPS_DIAG_ARRAY_LATE)  // (a hit's waves 4-7: the receptacle's array, in flight since
+        // the verdict, is in LDS before they arrive)
+        if (sc_join) sc_retire_array();
+#endif
         g.sync();
         if (t == 0) STAMP_NB(1);
 #if GS_MIXED
@@ -266,6 +270,15 @@
         else render_maps<9>(rc, g, geo, ovh, rb, paths, tile, cmap, early_tile, tail_cells, dist);
         if (t == 0) STAMP_NB(8);
     }
+#if defined(GS_CACHED) && defined(SIMAPS_DIAG_ARRAY_LATE)  // (a diagnostic build for tests/test_gpu_state_cache_prologue.py,
+    // never the product: a hit's waves 4-7 fetch the receptacle's array only here, with no work of their own
+    // left to hide it, so that their wait and the barrier below are all that stands between the fetch and
+    // the distance phase's reads -- without the wait those reads find the array unwritten)
+    if (sc_join) {
+        hit_array_dma<GS_ROOM_H, GS_ROOM_W>(dist, sc_rec, tid - 256);
+        sc_retire_array();
+    }
+#endif
     lds_barrier();
     STAMP(4);
 

@@ -8,21 +8,23 @@
 // waves 4-7 -- the twin's assignment swapped, so that on a hit the idle sweep waves are 4-7 and, with
 // the render waves 8-15, form waves 4-15: the one-source instance's render group (render_maps<12>).
 //
-// The verdict.  The sweep waves load the record's key and window words beside their early occupancy
-// loads, build the window words as the twin does and compare them bit for bit as they store them; a
-// thread that sees a difference (thread 0: in the key) ORs into the LDS word sc_diff before the sweep
-// group's first barrier, so every sweep wave reads the same verdict after it.  Thread 0 then publishes
-// it in sc_verdict (1 miss, 2 hit) behind a local release fence.
+// The verdict.  The sweep waves load the record's window words beside their early occupancy loads (wave 0
+// also the key), build the window words as the twin does and compare them bit for bit as they store
+// them; a thread that sees a difference (thread 0: in the key) ORs into the LDS word sc_diff before the
+// sweep group's first barrier, so every sweep wave reads the same verdict after it.  Thread 0 then
+// publishes it in sc_verdict (1 miss, 2 hit) behind a local release fence.
 //   miss: the twin's sweep track, which also rewrites the record: window words and free bits after the
 //         dilation, the receptacle's array by its own four waves when their rounds end (rec_export),
 //         key, results and the miss counter by thread 0 at the track's end.  A record is valid only
 //         with its key's magic, written last and only if no round cap was hit.
 //   hit:  waves 0-3 take the free bits from the record, initialise array 1 from them with the robot's
 //         snapped cell at 0, and sweep the robot's source alone; no dilation, no receptacle rounds.
-//         Waves 4-7 copy the record's array into array 0 and leave for the render track.
-//         What a hit takes from the record (free bits, array, results) is loaded on speculation with the
-//         key, after the verdict's own loads, so that a hit does not wait a second memory latency; a
-//         miss drops it (20 KB per workgroup read for nothing).
+//         Waves 4-7 start the copy of the record's array into array 0 (LDS-DMA, hit_array_dma) and leave
+//         for the render track with it in flight.
+//         The free bits, which the sweep track needs at once, are loaded on speculation with the key,
+//         after the verdict's own loads, so that a hit does not wait a second memory latency (a miss
+//         drops them: 0.7 KB).  The array, which nothing reads before the distance phase, is fetched
+//         after the verdict and by a hit only.
 //
 // The 8-or-12 barrier.  The render waves 8-15 run the parameter phase as in the twin and read
 // sc_verdict before the barrier that ends it, waiting (bounded, as wait_scratch) while it is 0.  The
@@ -57,53 +59,134 @@ __device__ __forceinline__ unsigned &sc_verdict(Shared &sh) { return sh.bar[3][3
 
 // what a sweep thread holds of its record from the kernel's start (8 sweep waves, G = 512)
 struct CachePre {
-    u32x4 key[4];                       // simaps_state_cache_header's key (3 words) and results
+    u32x4 key[4];                       // simaps_state_cache_header's key (3 words) and results: wave 0 only
     uint32_t w[OccLoad4<512>::NQ], w2;  // the window words this thread builds (win_from_dwords' mapping)
     // what a hit will take from the record, loaded on speculation (a miss drops it): waves 0-3 the free
-    // bits of their array rows (hit_rows), waves 4-7 their share of the receptacle's array (hit_copy)
-    u32x4 pf[5];
-    uint32_t pft;
+    // bits of their array rows (hit_rows)
+    u32x4 pf[3];
 };
-// a hit's work split: array row (t >> 4) + 16 k of thread t < 256, k < HIT_ROWS; 16-byte word
-// t2 + 256 k of the array for thread t2 = t - 256, k <= HIT_FULL (the last pass: t2 < HIT_LAST), and
-// the array's last cells & 3 floats one per thread
+// a hit's work split: array row (t >> 4) + 16 k of thread t < 256, k < ROWS; the receptacle's array by
+// waves 4-7 as PIECES whole 1 KiB pieces (one LDS-DMA wave-instruction each, piece p on wave 4 + p % 4)
+// and its last REST dwords by the first REST lanes of one wave
 template <int RH, int RW>
 struct HitSplit {
     static constexpr int cells = (RH + 2) * ((RW + 2) | 1);
-    static constexpr int ROWS = (RH + 2 + 15) / 16, FULL = cells / 4 / 256, LAST = cells / 4 - 256 * FULL, TAIL = cells & 3;
-    static_assert(ROWS <= 5 && FULL == 4, "CachePre::pf holds a thread's share");
+    static constexpr int ROWS = (RH + 2 + 15) / 16, PIECES = cells * 4 / 1024, REST = cells - 256 * PIECES;
+    static_assert(ROWS <= 3 && REST >= 0 && REST <= 64, "CachePre::pf holds a thread's rows; one wave-instruction for the rest");
+};
+
+// The record's buffer descriptor, for the builtin loads and, as its four words, for the written-out
+// LDS-DMA: base, stride 0, the record's length in bytes (0 for a missing record: every load reads 0
+// and touches no memory), raw 32-bit data format.  One place, so the two forms cannot disagree.
+template <int RH, int RW>
+struct RecordRsrc {
+    static constexpr unsigned FLAGS = 0x00020000u;
+    __device__ static __forceinline__ int len(const char *rec) { return rec ? record_bytes(RH, RW) : 0; }
+    __device__ static __forceinline__ __amdgpu_buffer_rsrc_t builtin(const char *rec)
+    {
+        return __builtin_amdgcn_make_buffer_rsrc((void *)rec, (short)0, len(rec), (int)FLAGS);
+    }
+    __device__ static __forceinline__ u32x4 words(const char *rec)  // (wave-uniform: scalar registers)
+    {
+        auto u = [](unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); };
+        const uint64_t base = (uint64_t)(uintptr_t)rec;
+        return u32x4{u((unsigned)base), u((unsigned)(base >> 32) & 0xffffu), u((unsigned)len(rec)), FLAGS};
+    }
 };
 
 // Range-checked loads (offset -1 and a missing record read 0, as cspace_load4's): all in flight at once.
+// Only what is used: the key by wave 0, a window word where the wave has a window row, the free bits
+// by waves 0-3; a condition that is the same for a whole wave is a branch, not an offset -1.
 template <int RH, int RW>
 __device__ __forceinline__ void cache_preload(CachePre &P, const char *rec, int t)
 {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void *)rec, (short)0, rec ? record_bytes(RH, RW) : 0, 0x00020000);
-    const int lane = t & 63, wave = t >> 6;
+    const __amdgpu_buffer_rsrc_t rs = RecordRsrc<RH, RW>::builtin(rec);
+    const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     constexpr int whM = RH + 2 * RMAX;
+    static_assert(whM % 2 == 0, "a wave's two window rows are in or out together");
 #pragma unroll
-    for (int k = 0; k < 4; k++) P.key[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * k, 0, 0);
+    for (int k = 0; k < 4; k++) {
+        P.key[k] = u32x4{0u, 0u, 0u, 0u};
+        if (wave == 0) P.key[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * k, 0, 0);
+    }
 #pragma unroll
     for (int q = 0; q < OccLoad4<512>::NQ; q++) {
         const int rr = 2 * (wave + 8 * q) + (lane >> 5);
-        P.w[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, rr < whM ? OFF_WIN + (rr * WIN_ROW_U32 + ((lane >> 3) & 3)) * 4 : -1, 0, 0);
+        P.w[q] = 0u;
+        if (2 * (wave + 8 * q) < whM)
+            P.w[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, OFF_WIN + (rr * WIN_ROW_U32 + ((lane >> 3) & 3)) * 4, 0, 0);
     }
     const int rr = t >> 2;
-    P.w2 = __builtin_amdgcn_raw_buffer_load_b32(rs, rr < whM ? OFF_WIN + (rr * WIN_ROW_U32 + 4) * 4 : -1, 0, 0);
+    P.w2 = 0u;
+    if (16 * wave < whM)
+        P.w2 = __builtin_amdgcn_raw_buffer_load_b32(rs, rr < whM ? OFF_WIN + (rr * WIN_ROW_U32 + 4) * 4 : -1, 0, 0);
     // (last: the verdict's loads above come back first)
     using HS = HitSplit<RH, RW>;
-    const bool rows = wave < 4;
-    const int t2 = t - 256, arr = off_rec(RH) + REC_HDR;
 #pragma unroll
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < HS::ROWS; k++) {
         const int r = (t >> 4) + 16 * k;
-        const int o_row = k < HS::ROWS && r >= 1 && r <= RH ? off_free(RH) + (r - 1) * 16 : -1;
-        const int o_arr = k < HS::FULL || t2 < HS::LAST ? arr + (t2 + 256 * k) * 16 : -1;
-        P.pf[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, rows ? o_row : o_arr, 0, 0);
+        P.pf[k] = u32x4{0u, 0u, 0u, 0u};
+        if (wave < 4) P.pf[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, r >= 1 && r <= RH ? off_free(RH) + (r - 1) * 16 : -1, 0, 0);
     }
-    P.pft = __builtin_amdgcn_raw_buffer_load_b32(rs, !rows && t2 < HS::TAIL ? arr + ((HS::cells & ~3) + t2) * 4 : -1, 0, 0);
 }
+
+// A hit's waves 4-7 (t2 = t - 256), after the verdict: the record's array straight into distance array 0
+// by LDS-DMA, nothing through registers.  Record and LDS image are both contiguous, so piece p is the
+// record's bytes [1024 p, 1024 p + 1024) of the array to the wave-uniform LDS base array + 1024 p, lane
+// l's 16 bytes at + 16 l.  The array's last REST dwords go as one 4-byte DMA of REST lanes: an inactive
+// lane writes nothing, so the DMA ends with the array and the render track's cell table behind it
+// (tail_cells_off: the next 16-byte boundary) is not written.  That bound rests on the arithmetic below
+// (static_assert), not on a test: the render track writes the table after the DMA has landed, so an
+// overrun would be overwritten unseen.  The loads are range-checked against the record like every
+// other (buffer loads through the record's descriptor).
+// Nothing reads array 0 before the distance phase; the issuing wave retires its DMA (sc_retire_array)
+// before a barrier that every reader passes.  The instruction is written out because the compiler
+// retires an LDS-DMA that it knows of at the wave's next LDS fence or read -- here the 12-wave barrier,
+// where a joining wave would make the render group wait for its DMA; it restores M0, which is the
+// compiler's.  vmcnt counts in order, so a wait the compiler places for a later load is only stricter.
+template <int BYTES>
+__device__ __forceinline__ void sc_dma_piece(u32x4 rs, unsigned lds_base, int voffset)
+{
+    static_assert(BYTES == 16 || BYTES == 4, "");
+    unsigned keep;
+    if (BYTES == 16)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep)
+                     : "v"(voffset), "s"(rs), "s"(lds_base)
+                     : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep)
+                     : "v"(voffset), "s"(rs), "s"(lds_base)
+                     : "memory");
+}
+template <int RH, int RW>
+__device__ __forceinline__ void hit_array_dma(float *dist, const char *rec, int t2)
+{
+    using HS = HitSplit<RH, RW>;
+    constexpr int arr = off_rec(RH) + REC_HDR;
+    static_assert(arr % 16 == 0 && OFF_DIST % 16 == 0, "16-byte pieces");
+    static_assert(arr + 1024 * HS::PIECES + 4 * HS::REST == arr + 4 * HS::cells && arr + 4 * HS::cells <= record_bytes(RH, RW),
+                  "the DMA covers the array and stays inside the record");
+    auto u = [](unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); };
+    const u32x4 rs = RecordRsrc<RH, RW>::words(rec);
+    const int lane = t2 & 63, wave = __builtin_amdgcn_readfirstlane(t2 >> 6);
+    const unsigned d = u((unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)reinterpret_cast<char *>(dist));
+#pragma unroll
+    for (int k = 0; k < (HS::PIECES + 3) / 4; k++) {
+        const int p = wave + 4 * k;
+        if (p < HS::PIECES) sc_dma_piece<16>(rs, d + 1024 * p, arr + 1024 * p + 16 * lane);
+    }
+    if (HS::REST > 0 && wave == (HS::PIECES & 3) && lane < HS::REST)
+        sc_dma_piece<4>(rs, d + 1024 * HS::PIECES, arr + 1024 * HS::PIECES + 4 * lane);
+}
+// The issuing wave's wait for hit_array_dma.  The product calls it on a joining wave between the 12-wave
+// barrier and the stamps' barrier, earlier than it must (any barrier up to the workgroup barrier ahead of
+// the distance phase would do): there the wave has issued next to nothing else (in the product nothing;
+// a stamp build's stamp stores, and intention_channel_order's loads where a configuration has them), so
+// vmcnt(0) is the DMA's count or at most stricter, and about 4 us of the wave's own work lie between
+// issue and wait.  Later, behind render_maps' stores, the same wait would expose their latency.
+__device__ __forceinline__ void sc_retire_array() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // win_from_dwords<512> with each stored word compared with the record's: true if one of this
 // thread's differs
@@ -230,13 +313,11 @@ __device__ __forceinline__ bool sweep_track_cached(Shared &sh, SsspScratch &S, f
     if (hit) {
         using HS = HitSplit<RH, RW>;
         static_assert(HS::cells == cells, "the same array");
-        if (t >= 256) {  // waves 4-7: the record's array -> distance array 0, the cell table's tail left alone
-            const int t2 = t - 256;
-            u32x4 *d4 = reinterpret_cast<u32x4 *>(dist);
-#pragma unroll
-            for (int k = 0; k < HS::FULL; k++) d4[t2 + 256 * k] = P.pf[k];
-            if (t2 < HS::LAST) d4[t2 + 256 * HS::FULL] = P.pf[HS::FULL];
-            if (t2 < HS::TAIL) reinterpret_cast<uint32_t *>(dist)[(cells & ~3) + t2] = P.pft;
+        if (t >= 256) {  // waves 4-7: the record's array -> distance array 0 (in flight when they join the render track)
+#ifndef SIMAPS_DIAG_ARRAY_LATE  // (the diagnostic build issues it at the last moment instead: get_state_body.inc, at the
+                                // workgroup barrier ahead of the distance phase)
+            hit_array_dma<RH, RW>(dist, rec, t - 256);
+#endif
             return true;
         }
         // waves 0-3: 16 lanes per array row as build_cspace writes it (free +inf, blocked / border -inf).
