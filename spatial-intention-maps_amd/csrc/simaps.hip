@@ -56,6 +56,7 @@
 #include "spec_store.h"
 #include "state16.h"
 #include "state_cache.h"
+#include "state_cache_store.h"
 #include "store.h"
 
 using namespace simaps;
@@ -4379,7 +4380,8 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
                      void *state, int state_dtype, int num_robots_per_env, const simaps_debug *dbg, void *stream,
                      const int64_t *dest = nullptr, int64_t capacity = 0, void *cache = nullptr, int cache_records = 0)
 {
-    // cache != nullptr: simaps_get_state_cached (simaps_state_cache.h), float32 and no store
+    // cache != nullptr: simaps_get_state_cached (simaps_state_cache.h), float32 and no store, or
+    // simaps_get_state_into_cached / simaps_get_state_as_cached (simaps_state_cache_store.h)
     // dest != nullptr: simaps_get_state_into (simaps_store.h) -- `state` is the caller's store of
     // `capacity` stacks (NULL allowed with capacity 0: check_state_into) and dest[n] agent n's row
     int rc = check_cfg(cfg);
@@ -4401,6 +4403,24 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     if (dbg) d = *dbg;
     // the store launches and the 16-bit launches: a compile-time instance where one matches the call
     // (simaps_spec_store.h, simaps_spec_store.inc); dest == nullptr is simaps_get_state_as
+    // -- and ahead of those, where the call brings a cache and would take instance S1's small-room twin,
+    // that twin with the state cache (simaps_state_cache_store.h, simaps_spec_cached_store.inc)
+    if ((dest || state_dtype != SIMAPS_STATE_F32) && cache && cache_records > 0 &&
+        simaps_state_cache_store::applies(*cfg, state_dtype, dest != nullptr, simaps_spec::any_debug(d))) {
+        if (state_dtype == SIMAPS_STATE_F32)
+            simaps_state_cache_store::launch_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
+                                                 (float *)state, capacity, dest, C, cx.fault_dev, cache, cache_records,
+                                                 (hipStream_t)stream);
+        else
+            (state_dtype == SIMAPS_STATE_BF16 ? simaps_state_cache_store::launch_bf16 : simaps_state_cache_store::launch_f16)(
+                *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity, dest, C,
+                cx.fault_dev, cache, cache_records, (hipStream_t)stream);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return fail(SIMAPS_EHIP, "%s launch: %s", dest ? "get_state_into_cached" : "get_state_as_cached",
+                        hipGetErrorString(e));
+        return 0;
+    }
     if (dest || state_dtype != SIMAPS_STATE_F32) {
         const int inst = simaps_spec_store::instance_as(*cfg, state_dtype, dest != nullptr, simaps_spec::any_debug(d));
         if (inst != SIMAPS_SPEC_GENERIC) {
@@ -5189,6 +5209,63 @@ int simaps_ctx_get_state_into(simaps_ctx *ctx, const simaps_config *cfg, int N, 
     if (const int rc = check_state_into(N, store, state_dtype, capacity, dest)) return rc;
     SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, store,
         state_dtype, num_robots_per_env, dbg, stream, dest, capacity));
+}
+
+// ---- simaps_state_cache_store.h
+int simaps_state_cache_store_abi_version(void) { return SIMAPS_STATE_CACHE_STORE_ABI_VERSION; }
+
+int simaps_state_cache_applies(const simaps_config *cfg, int state_dtype, int into, int has_debug)
+{
+    if (!cfg || (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16))
+        return SIMAPS_EINVAL;
+    return simaps_state_cache_store::applies(*cfg, state_dtype, into != 0, has_debug != 0) ? 1 : 0;
+}
+
+int simaps_get_state_into_cached(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                                 const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                                 const float *overhead, void *store, int state_dtype, int64_t capacity,
+                                 const int64_t *dest, int num_robots_per_env, const simaps_debug *dbg, void *stream,
+                                 void *cache, int cache_records)
+{
+    if (const int rc = check_state_cache(cache, cache_records)) return rc;
+    if (const int rc = check_state_into(N, store, state_dtype, capacity, dest)) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, store, state_dtype,
+                          num_robots_per_env, dbg, stream, dest, capacity, cache, cache_records);
+}
+int simaps_ctx_get_state_into_cached(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                     const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                                     const uint8_t *occupancy, const float *overhead, void *store, int state_dtype,
+                                     int64_t capacity, const int64_t *dest, int num_robots_per_env,
+                                     const simaps_debug *dbg, void *stream, void *cache, int cache_records)
+{
+    if (const int rc = check_state_cache(cache, cache_records)) return rc;
+    if (const int rc = check_state_into(N, store, state_dtype, capacity, dest)) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, store,
+        state_dtype, num_robots_per_env, dbg, stream, dest, capacity, cache, cache_records));
+}
+
+int simaps_get_state_as_cached(const simaps_config *cfg, int N, const simaps_agent *agents, const simaps_env *envs,
+                               const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
+                               const float *overhead, void *state, int state_dtype, int num_robots_per_env,
+                               const simaps_debug *dbg, void *stream, void *cache, int cache_records)
+{
+    if (const int rc = check_state_cache(cache, cache_records)) return rc;
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    simaps_ctx &cx = g_default_ctx;
+    return get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state, state_dtype,
+                          num_robots_per_env, dbg, stream, nullptr, 0, cache, cache_records);
+}
+int simaps_ctx_get_state_as_cached(simaps_ctx *ctx, const simaps_config *cfg, int N, const simaps_agent *agents,
+                                   const simaps_env *envs, const simaps_robot *robots, const double *paths,
+                                   const uint8_t *occupancy, const float *overhead, void *state, int state_dtype,
+                                   int num_robots_per_env, const simaps_debug *dbg, void *stream, void *cache,
+                                   int cache_records)
+{
+    if (const int rc = check_state_cache(cache, cache_records)) return rc;
+    if (const int rc = check_state_as(N, state, state_dtype)) return rc;
+    SIMAPS_ON_CTX(ctx, get_state_impl(cx, cfg, N, agents, envs, robots, paths, occupancy, overhead, state,
+        state_dtype, num_robots_per_env, dbg, stream, nullptr, 0, cache, cache_records));
 }
 
 int simaps_get_state_mixed_as(const simaps_config *cfgs, const int32_t *num_robots_per_env, int n_cfgs, int N,

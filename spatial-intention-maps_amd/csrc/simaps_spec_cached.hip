@@ -456,6 +456,8 @@ __device__ __forceinline__ bool sweep_track_cached(Shared &sh, SsspScratch &S, f
     return false;
 }
 
+#ifndef GS_CACHED_DEVICE  // (simaps_spec_cached_store.inc includes this file for the device code above only and
+                          // brings its own kernel and launcher: the store and 16-bit twins of the ones below)
 // MH x MW / RH x RW: the room class's map shape and room (simaps_spec.hip's GS_SPEC_ROOM arguments)
 template <int MH, int MW, int RH, int RW>
 __global__ void __launch_bounds__(NT) get_state_cached_kernel(
@@ -481,8 +483,10 @@ __global__ void __launch_bounds__(NT) get_state_cached_kernel(
 #include "get_state_body.inc"
 #undef GS_MIXED
 }
+#endif  // GS_CACHED_DEVICE
 }  // namespace
 
+#ifndef GS_CACHED_DEVICE
 namespace simaps_state_cache {
 void launch_get_state(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
                       const simaps_env *envs, const simaps_robot *robots, const double *paths,
@@ -501,3 +505,4 @@ int read_stamps(unsigned long long *host_out)
 }
 #endif
 }  // namespace simaps_state_cache
+#endif  // GS_CACHED_DEVICE

@@ -1,0 +1,3 @@
+// The bf16 cached instance of include/simaps_state_cache_store.h (simaps_spec_cached_store.inc), a translation unit of its own.
+#define SIMAPS_STORE_DTYPE 1
+#include "simaps_spec_cached_store.inc"

@@ -1,6 +1,6 @@
 """ctypes binding of libsimaps.so (the C ABI declared in include/simaps.h, include/simaps_ctx.h,
 include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h, include/simaps_spec.h, include/simaps_spec_room.h,
-include/simaps_spec_store.h, include/simaps_state_cache.h, include/simaps_ingest_seq.h and include/simaps_action_as.h).
+include/simaps_spec_store.h, include/simaps_state_cache.h, include/simaps_state_cache_store.h, include/simaps_ingest_seq.h and include/simaps_action_as.h).
 
 torch is imported FIRST so that libsimaps.so binds to the HIP runtime torch already loaded
 (both resolve SONAME libamdhip64.so.7): one runtime instance, so torch device pointers and
@@ -157,6 +157,13 @@ STATE_CACHE_HEADER_DTYPE = np.dtype([(n, '<i4') for n in (
     'reserved0', 'snap_i', 'snap_j', 'src_ok')] + [('dist_max', '<f4'), ('hits', '<u4'), ('misses', '<u4'),
                                                     ('reserved1', '<u4', (2,))], align=True)
 assert STATE_CACHE_HEADER_DTYPE.itemsize == 80
+
+# include/simaps_state_cache_store.h: the same cache for the store launches and the 16-bit launches (each
+# with its context twin), and the host-only query of which calls use it
+EXPORTED_STATE_CACHE_STORE = ('simaps_state_cache_store_abi_version', 'simaps_state_cache_applies',
+                              'simaps_get_state_into_cached', 'simaps_ctx_get_state_into_cached',
+                              'simaps_get_state_as_cached', 'simaps_ctx_get_state_as_cached')
+STATE_CACHE_STORE_ABI_VERSION = 1  # SIMAPS_STATE_CACHE_STORE_ABI_VERSION
 
 
 # include/simaps_ingest_seq.h: several frames per map slot in one launch, applied in order (with its
@@ -323,6 +330,22 @@ def _load(path=LIB_PATH):
         if vc != STATE_CACHE_ABI_VERSION:
             raise ImportError('libsimaps state_cache ABI version mismatch: %s has %d, this binding is %d'
                               % (path, vc, STATE_CACHE_ABI_VERSION))
+    if hasattr(L, 'simaps_get_state_into_cached'):  # (include/simaps_state_cache_store.h; absent only in an older revision's A/B build)
+        L.simaps_state_cache_store_abi_version.restype = i32
+        L.simaps_state_cache_applies.argtypes = [ctypes.POINTER(Config), i32, i32, i32]
+        L.simaps_state_cache_applies.restype = i32
+        # simaps_get_state_into's / simaps_get_state_as's list with the cache and its record count after stream
+        L.simaps_get_state_into_cached.argtypes = list(L.simaps_get_state_into.argtypes) + [vp, i32]
+        L.simaps_get_state_as_cached.argtypes = list(L.simaps_get_state_as.argtypes) + [vp, i32]
+        for name in ('get_state_into_cached', 'get_state_as_cached'):
+            getattr(L, 'simaps_' + name).restype = i32
+            twin = getattr(L, 'simaps_ctx_' + name)
+            twin.argtypes = [vp] + list(getattr(L, 'simaps_' + name).argtypes)
+            twin.restype = i32
+        vcs = L.simaps_state_cache_store_abi_version()
+        if vcs != STATE_CACHE_STORE_ABI_VERSION:
+            raise ImportError('libsimaps state_cache_store ABI version mismatch: %s has %d, this binding is %d'
+                              % (path, vcs, STATE_CACHE_STORE_ABI_VERSION))
     if hasattr(L, 'simaps_ingest_seq'):  # (include/simaps_ingest_seq.h; absent only in an older revision's A/B build)
         L.simaps_ingest_seq_abi_version.restype = i32
         # simaps_ingest's list with seq and num_seq after seg_raw

@@ -7,7 +7,7 @@ reference rebuilds its extension from its own source the same way (shortest_path
 
 Hashed: every `.hip` / `.h` / `.inc` file of spatial-intention-maps_amd/csrc, include/simaps.h,
 include/simaps_ctx.h, include/simaps_action.h, include/simaps_state16.h, include/simaps_store.h,
-include/simaps_spec.h, include/simaps_spec_room.h, include/simaps_spec_store.h, include/simaps_state_cache.h, include/simaps_ingest_seq.h and include/simaps_action_as.h, in sorted relative-path order, each as `path NUL content NUL`.  Comments count: any edit of a
+include/simaps_spec.h, include/simaps_spec_room.h, include/simaps_spec_store.h, include/simaps_state_cache.h, include/simaps_state_cache_store.h, include/simaps_ingest_seq.h and include/simaps_action_as.h, in sorted relative-path order, each as `path NUL content NUL`.  Comments count: any edit of a
 kernel source makes the library stale until it is rebuilt.
 """
 import hashlib
@@ -32,6 +32,7 @@ def source_files(pkg_root=PKG_ROOT, repo_root=None):
     files.append(('include/simaps_spec_room.h', os.path.join(repo_root, 'include', 'simaps_spec_room.h')))
     files.append(('include/simaps_spec_store.h', os.path.join(repo_root, 'include', 'simaps_spec_store.h')))
     files.append(('include/simaps_state_cache.h', os.path.join(repo_root, 'include', 'simaps_state_cache.h')))
+    files.append(('include/simaps_state_cache_store.h', os.path.join(repo_root, 'include', 'simaps_state_cache_store.h')))
     files.append(('include/simaps_ingest_seq.h', os.path.join(repo_root, 'include', 'simaps_ingest_seq.h')))
     files.append(('include/simaps_action_as.h', os.path.join(repo_root, 'include', 'simaps_action_as.h')))
     return sorted(files)

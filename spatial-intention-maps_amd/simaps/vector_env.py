@@ -296,7 +296,10 @@ class VectorEnvObservations:
         dest: an int64 device tensor with one row of the store per map slot (self.slot[(env, robot)]
         order), -1 for a robot that is not to be rendered -- never read on the host, so which robots
         act may be decided on the device and the call captured in a graph; or [env][robot] ints with
-        None for "not this robot" (checked for range and duplicates: ValueError)."""
+        None for "not this robot" (checked for range and duplicates: ValueError).
+        With self.batch.state_cache = 'all' the launch passes the batch's state cache
+        (StateBatch.render_into): rows bit for bit the same, sooner while a robot's map is unchanged,
+        whatever `dest` skips; by default it goes without."""
         if not isinstance(dest, torch.Tensor):
             if len(dest) != self.num_envs or any(len(d) != len(s['robots']) for d, s in zip(dest, self.batch.scenes)):
                 raise ValueError('dest must be [env][robot] rows (None: not this robot), or a device tensor')

@@ -444,7 +444,8 @@ def bench_state16(args):
     reports its rounds' median, min and max.  (c) and (d) do (a)'s work with fewer bytes written, so
     they are expected within (a)'s own min..max of this session or below; (b) - (c) is the gain."""
     scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
-    b = batch.StateBatch(scenes, layout='chw')
+    # --state-cache: the 16-bit renders pass the batch's state cache too (off by default: DESIGN.md section 5)
+    b = batch.StateBatch(scenes, layout='chw', state_cache='all' if args.state_cache else True)
     f32 = b.alloc_state()
     o16 = {dt: b.alloc_state(dtype=dt) for dt in (torch.bfloat16, torch.float16)}
     cast = b.alloc_state(dtype=torch.bfloat16)
@@ -482,7 +483,8 @@ def bench_state16(args):
         line = {'row': 'state16', 'variant': name, 'config': args.config, 'stacks': b.N, 'channels': b.C, 'layout': 'chw',
                 'median_us': float(np.median(v)), 'min_us': min(v), 'max_us': max(v), 'rounds_us': [round(x, 3) for x in v],
                 'state_bytes_written': elems * (4 if name.startswith(('a_', 'b_')) else 2),
-                'cast_pass_bytes': elems * 6 if name.startswith('b_') else 0, 'reps_per_round': args.reps}
+                'cast_pass_bytes': elems * 6 if name.startswith('b_') else 0, 'reps_per_round': args.reps,
+                'state_cache': 'all' if args.state_cache else 'float32 render only'}
         if name in ('c_bf16', 'd_f16'):
             line['a_spread_us'] = [a_lo, a_hi]
             line['median_within_or_below_a_spread'] = bool(np.median(v) <= a_hi)
@@ -492,7 +494,8 @@ def bench_state16(args):
         print(json.dumps(line), flush=True)
     lines.append({'row': 'state16_note', 'note': 'device time per call: HIP events around reps_per_round calls queued '
                   'behind two 8192^3 float32 matmuls, after 20 warm-up calls per variant; the variants alternate round '
-                  'by round in one process; b = float32 render + copy_ into a preallocated bfloat16 batch'})
+                  'by round in one process; b = float32 render + copy_ into a preallocated bfloat16 batch; state_cache: whether '
+                  'the bf16 / fp16 renders pass the state cache (--state-cache) or only the float32 render does (default)'})
     with open(args.out, 'w') as f:
         f.write(''.join(json.dumps(x) + '\n' for x in lines))
 
@@ -507,7 +510,8 @@ def bench_store(args):
     process, each reporting its rounds' median, min and max.  No ratio is fixed in advance: (b) is
     compared with (a)'s min..max and (d) with (c)'s."""
     scenes = [synthetic.make_scene(args.config, e) for e in range(args.envs)]
-    b = batch.StateBatch(scenes, layout='chw')
+    # --state-cache: render_into and the bf16 renders pass the batch's state cache (off by default: DESIGN.md section 5)
+    b = batch.StateBatch(scenes, layout='chw', state_cache='all' if args.state_cache else True)
     dt = torch.bfloat16
     store = b.alloc_store(args.capacity, dtype=dt).zero_()
     check = torch.zeros_like(store)
@@ -571,7 +575,8 @@ def bench_store(args):
         line = {'row': 'store', 'variant': name, 'config': args.config, 'agents_launched': b.N if name[0] != 'c' else n,
                 'stacks_stored': n, 'channels': b.C, 'layout': 'chw', 'store_dtype': 'bfloat16',
                 'store_capacity': args.capacity, 'median_us': float(np.median(v)), 'min_us': min(v), 'max_us': max(v),
-                'rounds_us': [round(x, 3) for x in v], 'reps_per_round': args.reps}
+                'rounds_us': [round(x, 3) for x in v], 'reps_per_round': args.reps,
+                'state_cache': 'all' if args.state_cache else 'float32 render only'}
         if name in against:
             o = us[against[name]]
             line['against'] = against[name]
@@ -584,7 +589,8 @@ def bench_store(args):
                   'behind two 8192^3 float32 matmuls, after 20 warm-up calls per variant; the variants alternate round '
                   'by round in one process; a / c = render into a preallocated bf16 batch + store.index_copy_(0, dest, '
                   'batch); b / d = one simaps_get_state_into launch; the destination rows are a fixed random choice '
-                  'among the store\'s rows'})
+                  'among the store\'s rows; state_cache: whether these launches pass the state cache (--state-cache; maps '
+                  'unchanged, so every launch after the first is a hit) or go without (default)'})
     with open(args.out, 'w') as f:
         f.write(''.join(json.dumps(x) + '\n' for x in lines))
 
@@ -768,6 +774,7 @@ if __name__ == '__main__':
     if '--state16' in sys.argv:
         ap = argparse.ArgumentParser()
         ap.add_argument('--state16', action='store_true')
+        ap.add_argument('--state-cache', action='store_true', help='the store / 16-bit launches pass the state cache')
         ap.add_argument('--config', default='lifting_4-small_divider')
         ap.add_argument('--envs', type=int, default=64)
         ap.add_argument('--rounds', type=int, default=15)
@@ -778,6 +785,7 @@ if __name__ == '__main__':
     if '--store' in sys.argv:
         ap = argparse.ArgumentParser()
         ap.add_argument('--store', action='store_true')
+        ap.add_argument('--state-cache', action='store_true', help='the store / 16-bit launches pass the state cache')
         ap.add_argument('--config', default='lifting_4-small_divider')
         ap.add_argument('--envs', type=int, default=64)
         ap.add_argument('--capacity', type=int, default=4096)
