@@ -4261,6 +4261,21 @@ int check_cfg(const simaps_config *c)
         return fail(SIMAPS_EINVAL, "bad rotate_rounding %d", c->rotate_rounding);
     return 0;
 }
+
+// a SIMAPS_STATE_* element type (simaps_state16.h); the callers have their own error texts
+bool state_dtype_ok(int dtype)
+{
+    return dtype == SIMAPS_STATE_F32 || dtype == SIMAPS_STATE_BF16 || dtype == SIMAPS_STATE_F16;
+}
+
+// what every get_state launch asks of the geometry: each robot type's cspace radius within the
+// window's margin
+int check_cspace_radii(const Geometry &geo)
+{
+    for (int t = 0; t < 4; t++)
+        if (geo.cspace_r[t] > RMAX) return fail(SIMAPS_EUNSUPPORTED, "cspace radius %d > %d", geo.cspace_r[t], RMAX);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -4386,8 +4401,7 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     // `capacity` stacks (NULL allowed with capacity 0: check_state_into) and dest[n] agent n's row
     int rc = check_cfg(cfg);
     const Geometry &geo = geometry();
-    for (int t = 0; t < 4; t++)
-        if (geo.cspace_r[t] > RMAX) return fail(SIMAPS_EUNSUPPORTED, "cspace radius %d > %d", geo.cspace_r[t], RMAX);
+    if (const int rr = check_cspace_radii(geo)) return rr;  // (answered ahead of check_cfg's)
     if (rc) return rc;
     if (N < 0) return fail(SIMAPS_EINVAL, "N < 0");
     if (N == 0) return 0;
@@ -4396,97 +4410,73 @@ static int get_state_impl(simaps_ctx &cx, const simaps_config *cfg, int N, const
     if ((cfg->use_intention_map || cfg->use_history_map) && !paths) return fail(SIMAPS_EINVAL, "paths is NULL");
     if (cfg->use_intention_channels && (num_robots_per_env < 1 || num_robots_per_env > SIMAPS_MAX_ROBOTS))
         return fail(SIMAPS_EINVAL, "intention channels need num_robots_per_env in [1, %d]", SIMAPS_MAX_ROBOTS);
-    const int C = simaps_num_channels(cfg, num_robots_per_env > 0 ? num_robots_per_env : 1);
     if ((rc = pending_faults(cx))) return rc;
-    simaps_debug d;
-    memset(&d, 0, sizeof(d));
-    if (dbg) d = *dbg;
-    // the store launches and the 16-bit launches: a compile-time instance where one matches the call
-    // (simaps_spec_store.h, simaps_spec_store.inc); dest == nullptr is simaps_get_state_as
-    // -- and ahead of those, where the call brings a cache and would take instance S1's small-room twin,
-    // that twin with the state cache (simaps_state_cache_store.h, simaps_spec_cached_store.inc)
-    if ((dest || state_dtype != SIMAPS_STATE_F32) && cache && cache_records > 0 &&
-        simaps_state_cache_store::applies(*cfg, state_dtype, dest != nullptr, simaps_spec::any_debug(d))) {
-        if (state_dtype == SIMAPS_STATE_F32)
-            simaps_state_cache_store::launch_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
-                                                 (float *)state, capacity, dest, C, cx.fault_dev, cache, cache_records,
-                                                 (hipStream_t)stream);
-        else
-            (state_dtype == SIMAPS_STATE_BF16 ? simaps_state_cache_store::launch_bf16 : simaps_state_cache_store::launch_f16)(
-                *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity, dest, C,
-                cx.fault_dev, cache, cache_records, (hipStream_t)stream);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return fail(SIMAPS_EHIP, "%s launch: %s", dest ? "get_state_into_cached" : "get_state_as_cached",
-                        hipGetErrorString(e));
-        return 0;
-    }
-    if (dest || state_dtype != SIMAPS_STATE_F32) {
-        const int inst = simaps_spec_store::instance_as(*cfg, state_dtype, dest != nullptr, simaps_spec::any_debug(d));
-        if (inst != SIMAPS_SPEC_GENERIC) {
-            if (state_dtype == SIMAPS_STATE_F32)
-                simaps_spec_store::launch_f32(inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
-                                              (float *)state, capacity, dest, C, cx.fault_dev, (hipStream_t)stream);
-            else
-                (state_dtype == SIMAPS_STATE_BF16 ? simaps_spec_store::launch_bf16 : simaps_spec_store::launch_f16)(
-                    inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity,
-                    dest, C, cx.fault_dev, (hipStream_t)stream);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess)
-                return fail(SIMAPS_EHIP, "%s launch: %s", dest ? "get_state_into" : "get_state_as", hipGetErrorString(e));
-            return 0;
-        }
-    }
-    if (dest) {  // simaps_get_state_into: one launch of the element type's kernel (simaps_store.inc)
-        if (state_dtype == SIMAPS_STATE_F32)
-            simaps_store::launch_get_state_into_f32(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
-                                                    (float *)state, capacity, dest, C, d, cx.fault_dev,
-                                                    (hipStream_t)stream);
-        else
-            (state_dtype == SIMAPS_STATE_BF16 ? simaps_store::launch_get_state_into_bf16
-                                              : simaps_store::launch_get_state_into_f16)(
-                *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, capacity, dest, C, d,
-                cx.fault_dev, (hipStream_t)stream);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_into launch: %s", hipGetErrorString(e));
-        return 0;
-    }
-    if (state_dtype != SIMAPS_STATE_F32) {  // simaps_get_state_as: the 16-bit instantiations (simaps_state16.inc)
-        (state_dtype == SIMAPS_STATE_BF16 ? simaps_state16::launch_get_state_bf16 : simaps_state16::launch_get_state_f16)(
-            *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead, (uint16_t *)state, C, d, cx.fault_dev,
-            (hipStream_t)stream);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_as launch: %s", hipGetErrorString(e));
-        return 0;
-    }
-    // a compile-time instance of the kernel where one matches the call (simaps_spec.h, simaps_spec.hip)
-    const int inst = simaps_spec::instance_of(*cfg, simaps_spec::any_debug(d));
-    // the instance that reuses an unchanged map's cspace and receptacle distances, where the call brings
-    // a cache and would take that instance's twin (simaps_state_cache.h, simaps_spec_cached.hip)
-    if (cache && cache_records > 0 && simaps_state_cache::uses_cache(*cfg, simaps_spec::any_debug(d))) {
+    // the launch, described once for whichever family takes it (get_state_launch.h)
+    simaps::GetStateLaunch L;
+    L.cfg = cfg;
+    L.geo = &geo;
+    L.N = N;
+    L.agents = agents;
+    L.envs = envs;
+    L.robots = robots;
+    L.paths = paths;
+    L.occupancy = occupancy;
+    L.overhead = overhead;
+    L.state = state;
+    L.state_dtype = state_dtype;
+    L.capacity = capacity;
+    L.dest = dest;
+    L.C = simaps_num_channels(cfg, num_robots_per_env > 0 ? num_robots_per_env : 1);
+    memset(&L.dbg, 0, sizeof(L.dbg));
+    if (dbg) L.dbg = *dbg;
+    L.fault = cx.fault_dev;
+    L.cache = cache;
+    L.cache_records = cache_records;
+    L.stream = (hipStream_t)stream;
+    const bool into = dest != nullptr, f32 = state_dtype == SIMAPS_STATE_F32, cached = cache && cache_records > 0;
+    const bool any_dbg = simaps_spec::any_debug(L.dbg);
+    const char *what;  // the launch's name in the error text
+    int inst;
+    if ((into || !f32) && cached && simaps_state_cache_store::applies(*cfg, state_dtype, into, any_dbg)) {
+        // a store launch or a 16-bit launch that brings a cache and would take instance S1's small-room
+        // twin: that twin with the state cache (simaps_state_cache_store.h, simaps_spec_cached_store.inc)
+        what = into ? "get_state_into_cached" : "get_state_as_cached";
+        simaps_state_cache_store::launch(L);
+    } else if ((into || !f32) &&
+               (inst = simaps_spec_store::instance_as(*cfg, state_dtype, into, any_dbg)) != SIMAPS_SPEC_GENERIC) {
+        // the store launches and the 16-bit launches: a compile-time instance where one matches the call
+        // (simaps_spec_store.h, simaps_spec_store.inc); dest == nullptr is simaps_get_state_as
+        what = into ? "get_state_into" : "get_state_as";
+        simaps_spec_store::launch(inst, L);
+    } else if (into) {  // simaps_get_state_into: the element type's generic kernel (simaps_store.inc)
+        what = "get_state_into";
+        simaps_store::launch_get_state_into(L);
+    } else if (!f32) {  // simaps_get_state_as: the 16-bit instantiations (simaps_state16.inc)
+        what = "get_state_as";
+        simaps_state16::launch_get_state(L);
+    } else if (cached && simaps_state_cache::uses_cache(*cfg, any_dbg)) {
+        // the instance that reuses an unchanged map's cspace and receptacle distances, where the call brings
+        // a cache and would take that instance's twin (simaps_state_cache.h, simaps_spec_cached.hip)
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
         g_stamp_instance = STAMP_INSTANCE_CACHED;
 #endif
-        simaps_state_cache::launch_get_state(*cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
-                                             (float *)state, C, cx.fault_dev, cache, cache_records, (hipStream_t)stream);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_cached launch: %s", hipGetErrorString(e));
-        return 0;
-    }
+        what = "get_state_cached";
+        simaps_state_cache::launch_get_state(L);
+    } else {
+        // a compile-time instance of the kernel where one matches the call (simaps_spec.h, simaps_spec.hip)
+        inst = simaps_spec::instance_of(*cfg, any_dbg);
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
-    g_stamp_instance = inst;
+        g_stamp_instance = inst;
 #endif
-    if (inst != SIMAPS_SPEC_GENERIC) {
-        simaps_spec::launch_get_state(inst, *cfg, geo, N, agents, envs, robots, paths, occupancy, overhead,
-                                      (float *)state, C, cx.fault_dev, (hipStream_t)stream);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
-        return 0;
+        what = "get_state";
+        if (inst != SIMAPS_SPEC_GENERIC)
+            simaps_spec::launch_get_state(inst, L);
+        else
+            hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), 0, L.stream, *cfg, geo, agents, envs, robots, paths,
+                               occupancy, overhead, (float *)state, L.C, L.dbg, cx.fault_dev);
     }
-    hipLaunchKernelGGL(get_state_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, *cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, (float *)state, C, d, cx.fault_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(SIMAPS_EHIP, "%s launch: %s", what, hipGetErrorString(e));
     return 0;
 }
 
@@ -4500,8 +4490,7 @@ static int get_state_mixed_impl(simaps_ctx &cx, const simaps_config *cfgs, const
     if (!cfgs || n_cfgs < 1 || n_cfgs > SIMAPS_MAX_MIXED)
         return fail(SIMAPS_EINVAL, "n_cfgs %d not in [1, %d]", n_cfgs, SIMAPS_MAX_MIXED);
     const Geometry &geo = geometry();
-    for (int t = 0; t < 4; t++)
-        if (geo.cspace_r[t] > RMAX) return fail(SIMAPS_EUNSUPPORTED, "cspace radius %d > %d", geo.cspace_r[t], RMAX);
+    if (const int rc = check_cspace_radii(geo)) return rc;
     simaps_mixed::MixedCfgs mx;
     memset(&mx, 0, sizeof(mx));
     bool any_paths = false;
@@ -4522,14 +4511,27 @@ static int get_state_mixed_impl(simaps_ctx &cx, const simaps_config *cfgs, const
         return fail(SIMAPS_EINVAL, "NULL buffer");
     if (any_paths && !paths) return fail(SIMAPS_EINVAL, "paths is NULL");
     if (const int rc = pending_faults(cx)) return rc;
+    simaps_mixed::MixedLaunch L;
+    L.mx = &mx;
+    L.geo = &geo;
+    L.N = N;
+    L.agents = agents;
+    L.agent_cfg = agent_cfg;
+    L.envs = envs;
+    L.robots = robots;
+    L.paths = paths;
+    L.occupancy = occupancy;
+    L.map_off = map_off;
+    L.overhead = overhead;
+    L.state = state;
+    L.state_dtype = state_dtype;
+    L.out_off = out_off;
+    L.fault = cx.fault_dev;
+    L.stream = (hipStream_t)stream;
     if (state_dtype != SIMAPS_STATE_F32)  // simaps_get_state_mixed_as: the 16-bit instantiations (simaps_store.inc)
-        (state_dtype == SIMAPS_STATE_BF16 ? simaps_store::launch_get_state_mixed_bf16
-                                          : simaps_store::launch_get_state_mixed_f16)(
-            mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off, overhead, (uint16_t *)state, out_off,
-            cx.fault_dev, (hipStream_t)stream);
+        simaps_store::launch_get_state_mixed16(L);
     else
-        simaps_mixed::launch_get_state_mixed(mx, geo, N, agents, agent_cfg, envs, robots, paths, occupancy, map_off,
-                                             overhead, (float *)state, out_off, cx.fault_dev, (hipStream_t)stream);
+        simaps_mixed::launch_get_state_mixed(L);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SIMAPS_EHIP, "get_state_mixed launch: %s", hipGetErrorString(e));
     return 0;
@@ -4698,7 +4700,7 @@ static int store_new_action_as_impl(simaps_ctx &cx, const simaps_config *cfg, in
     int rc = store_new_action_args(cfg, N, agents, envs, robots, paths, occupancy, q, q_off, actions_in, flags, max_points,
                                    out_action, out_source, out_target, out_xy, out_heading, out_count);
     if (rc) return rc;
-    if (q_dtype != SIMAPS_STATE_F32 && q_dtype != SIMAPS_STATE_BF16 && q_dtype != SIMAPS_STATE_F16)
+    if (!state_dtype_ok(q_dtype))
         return fail(SIMAPS_EINVAL, "q_dtype %d: SIMAPS_STATE_F32, SIMAPS_STATE_BF16 or SIMAPS_STATE_F16", q_dtype);
     if (eps && !rng) return fail(SIMAPS_EINVAL, "eps without rng");
     if (N == 0) return 0;
@@ -5127,7 +5129,7 @@ int simaps_state16_abi_version(void) { return SIMAPS_STATE16_ABI_VERSION; }
 // what simaps_get_state_as checks on top of simaps_get_state (N <= 0 is get_state_impl's to answer)
 static int check_state_as(int N, const void *state, int state_dtype)
 {
-    if (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16)
+    if (!state_dtype_ok(state_dtype))
         return fail(SIMAPS_EINVAL, "unknown state_dtype %d (SIMAPS_STATE_F32, _BF16 or _F16)", state_dtype);
     if (N > 0 && !state) return fail(SIMAPS_EINVAL, "state is NULL");
     if (N > 0 && ((uintptr_t)state & 15u)) return fail(SIMAPS_EINVAL, "state %p is not aligned to 16 bytes", state);
@@ -5180,7 +5182,7 @@ int simaps_store_abi_version(void) { return SIMAPS_STORE_ABI_VERSION; }
 // what simaps_get_state_into checks on top of simaps_get_state (N <= 0 is get_state_impl's to answer)
 static int check_state_into(int N, const void *store, int state_dtype, int64_t capacity, const int64_t *dest)
 {
-    if (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16)
+    if (!state_dtype_ok(state_dtype))
         return fail(SIMAPS_EINVAL, "unknown state_dtype %d (SIMAPS_STATE_F32, _BF16 or _F16)", state_dtype);
     if (capacity < 0) return fail(SIMAPS_EINVAL, "capacity %lld < 0", (long long)capacity);
     if (N > 0 && !dest) return fail(SIMAPS_EINVAL, "dest is NULL");
@@ -5216,8 +5218,7 @@ int simaps_state_cache_store_abi_version(void) { return SIMAPS_STATE_CACHE_STORE
 
 int simaps_state_cache_applies(const simaps_config *cfg, int state_dtype, int into, int has_debug)
 {
-    if (!cfg || (state_dtype != SIMAPS_STATE_F32 && state_dtype != SIMAPS_STATE_BF16 && state_dtype != SIMAPS_STATE_F16))
-        return SIMAPS_EINVAL;
+    if (!cfg || !state_dtype_ok(state_dtype)) return SIMAPS_EINVAL;
     return simaps_state_cache_store::applies(*cfg, state_dtype, into != 0, has_debug != 0) ? 1 : 0;
 }
 

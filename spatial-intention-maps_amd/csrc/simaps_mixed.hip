@@ -30,13 +30,9 @@ __global__ void __launch_bounds__(NT) get_state_mixed_kernel(
 }  // namespace
 
 namespace simaps_mixed {
-void launch_get_state_mixed(const MixedCfgs &mx, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                            const int32_t *agent_cfg, const simaps_env *envs, const simaps_robot *robots,
-                            const double *paths, const uint8_t *occupancy, const int64_t *map_off,
-                            const float *overhead, float *state, const int64_t *out_off, unsigned *fault,
-                            hipStream_t stream)
+void launch_get_state_mixed(const MixedLaunch &L)
 {
-    hipLaunchKernelGGL(get_state_mixed_kernel, dim3(N), dim3(NT), 0, stream, mx, geo, agents, agent_cfg, envs, robots,
-                       paths, occupancy, map_off, overhead, state, out_off, fault);
+    hipLaunchKernelGGL(get_state_mixed_kernel, dim3(L.N), dim3(NT), 0, L.stream, *L.mx, *L.geo, L.agents, L.agent_cfg,
+                       L.envs, L.robots, L.paths, L.occupancy, L.map_off, L.overhead, (float *)L.state, L.out_off, L.fault);
 }
 }  // namespace simaps_mixed

@@ -42,6 +42,7 @@
 #define GS_ROOM_W RW
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
+#include "get_state_instance.h"
 #include "spec.h"
 
 namespace {
@@ -54,20 +55,7 @@ __global__ void __launch_bounds__(NT) get_state_spec_kernel(
     const float *__restrict__ overhead, float *__restrict__ state, int C, unsigned *fault)
 {
     simaps_config cfg = cfg_in;
-    cfg.use_robot_map = 1;
-    cfg.use_distance_to_receptacle_map = 0;
-    cfg.use_shortest_path_to_receptacle_map = REC;
-    cfg.use_shortest_path_map = 1;
-    cfg.use_intention_map = 1;
-    cfg.use_history_map = 0;
-    cfg.use_intention_channels = 0;
-    cfg.layout_chw = 1;
-    if (RH) {  // GS_SPEC_ROOM
-        cfg.H = MH;
-        cfg.W = MW;
-        cfg.room_h = RH;
-        cfg.room_w = RW;
-    }
+    fix_instance_fields<REC, MH, MW, RH, RW>(cfg);  // (RH != 0: GS_SPEC_ROOM)
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #include "get_state_body.inc"
@@ -79,19 +67,16 @@ using spec_kernel_t = void (*)(simaps_config, Geometry, const simaps_agent *, co
 }  // namespace
 
 namespace simaps_spec {
-void launch_get_state(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                      const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                      const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
-                      hipStream_t stream)
+void launch_get_state(int id, const simaps::GetStateLaunch &L)
 {
     spec_kernel_t k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1> : get_state_spec_kernel<0>;
     // the room-class twin of S1 / S2 where cfg's shape matches a class exactly (spec.h)
-    if (room_class_of(cfg) == SIMAPS_ROOM_SMALL) {
+    if (room_class_of(*L.cfg) == SIMAPS_ROOM_SMALL) {
         constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
         k = id == SIMAPS_SPEC_S1 ? get_state_spec_kernel<1, MH, MW, RH, RW> : get_state_spec_kernel<0, MH, MW, RH, RW>;
     }
-    hipLaunchKernelGGL(k, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy, overhead,
-                       state, C, fault);
+    hipLaunchKernelGGL(k, dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo, L.agents, L.envs, L.robots, L.paths,
+                       L.occupancy, L.overhead, (float *)L.state, L.C, L.fault);
 }
 
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)

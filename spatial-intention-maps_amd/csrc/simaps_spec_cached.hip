@@ -41,6 +41,7 @@
 #define GS_ROOM_W RW
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
+#include "get_state_instance.h"
 #include "spec.h"
 #include "state_cache.h"
 
@@ -465,19 +466,8 @@ __global__ void __launch_bounds__(NT) get_state_cached_kernel(
     const simaps_robot *__restrict__ robots, const double *__restrict__ paths, const uint8_t *__restrict__ occupancy,
     const float *__restrict__ overhead, float *__restrict__ state, int C, unsigned *fault, char *cache, int cache_records)
 {
-    simaps_config cfg = cfg_in;  // (instance S1's fixed fields, as simaps_spec.hip sets them)
-    cfg.use_robot_map = 1;
-    cfg.use_distance_to_receptacle_map = 0;
-    cfg.use_shortest_path_to_receptacle_map = 1;
-    cfg.use_shortest_path_map = 1;
-    cfg.use_intention_map = 1;
-    cfg.use_history_map = 0;
-    cfg.use_intention_channels = 0;
-    cfg.layout_chw = 1;
-    cfg.H = MH;
-    cfg.W = MW;
-    cfg.room_h = RH;
-    cfg.room_w = RW;
+    simaps_config cfg = cfg_in;
+    fix_instance_fields<1, MH, MW, RH, RW>(cfg);  // (instance S1 in the room class, as simaps_spec.hip's twin)
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #include "get_state_body.inc"
@@ -488,14 +478,12 @@ __global__ void __launch_bounds__(NT) get_state_cached_kernel(
 
 #ifndef GS_CACHED_DEVICE
 namespace simaps_state_cache {
-void launch_get_state(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                      const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                      const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
-                      void *cache, int cache_records, hipStream_t stream)
+void launch_get_state(const simaps::GetStateLaunch &L)
 {
     constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
-    hipLaunchKernelGGL((get_state_cached_kernel<MH, MW, RH, RW>), dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs,
-                       robots, paths, occupancy, overhead, state, C, fault, (char *)cache, cache_records);
+    hipLaunchKernelGGL((get_state_cached_kernel<MH, MW, RH, RW>), dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo,
+                       L.agents, L.envs, L.robots, L.paths, L.occupancy, L.overhead, (float *)L.state, L.C, L.fault,
+                       (char *)L.cache, L.cache_records);
 }
 
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)

@@ -53,36 +53,17 @@ __global__ void __launch_bounds__(NT) GSC_KERNEL(
     const float *__restrict__ overhead, GSC_ELEM *__restrict__ state, int64_t capacity,
     const int64_t *__restrict__ dest, int C, unsigned *fault, char *cache, int cache_records)
 {
-    // the workgroup's row of the store: one value per workgroup, read before anything else
-    // (simaps_spec_store.inc), the record included
+    // the workgroup's row of the store, read before anything else, the record included (store_row:
+    // get_state_instance.h; a workgroup that returns here leaves its record untouched)
 #ifdef GSC_PLAIN
     int64_t into_row = blockIdx.x;  // (simaps_get_state_as_cached: no dest, stack n at row n)
-    if (dest) {
-        into_row = dest[blockIdx.x];
+    if (dest && !store_row(dest, capacity, fault, into_row)) return;
 #else
-    const int64_t into_row = dest[blockIdx.x];
-    {
+    int64_t into_row;
+    if (!store_row(dest, capacity, fault, into_row)) return;
 #endif
-        if (into_row == -1) return;  // not this agent: nothing written, nothing posted, the record untouched
-        if ((uint64_t)into_row >= (uint64_t)capacity) {
-            // a row outside the store: reported, and the workgroup writes nothing
-            if (threadIdx.x == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GET_STATE_INTO, blockIdx.x);
-            return;
-        }
-    }
-    simaps_config cfg = cfg_in;  // (instance S1's fixed fields and the room class's, as get_state_cached_kernel)
-    cfg.use_robot_map = 1;
-    cfg.use_distance_to_receptacle_map = 0;
-    cfg.use_shortest_path_to_receptacle_map = 1;
-    cfg.use_shortest_path_map = 1;
-    cfg.use_intention_map = 1;
-    cfg.use_history_map = 0;
-    cfg.use_intention_channels = 0;
-    cfg.layout_chw = 1;
-    cfg.H = MH;
-    cfg.W = MW;
-    cfg.room_h = RH;
-    cfg.room_w = RW;
+    simaps_config cfg = cfg_in;
+    fix_instance_fields<1, MH, MW, RH, RW>(cfg);  // (instance S1 in the room class, as get_state_cached_kernel)
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #define GS_INTO 1
@@ -97,13 +78,11 @@ __global__ void __launch_bounds__(NT) GSC_KERNEL(
 }  // namespace
 
 namespace simaps_state_cache_store {
-void GSC_LAUNCH(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, GSC_ELEM *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                void *cache, int cache_records, hipStream_t stream)
+void GSC_LAUNCH(const simaps::GetStateLaunch &L)
 {
     constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
-    hipLaunchKernelGGL((GSC_KERNEL<MH, MW, RH, RW>), dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths,
-                       occupancy, overhead, store, capacity, dest, C, fault, (char *)cache, cache_records);
+    hipLaunchKernelGGL((GSC_KERNEL<MH, MW, RH, RW>), dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo, L.agents, L.envs,
+                       L.robots, L.paths, L.occupancy, L.overhead, (GSC_ELEM *)L.state, L.capacity, L.dest, L.C, L.fault,
+                       (char *)L.cache, L.cache_records);
 }
 }  // namespace simaps_state_cache_store

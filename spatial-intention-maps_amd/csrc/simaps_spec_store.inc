@@ -8,10 +8,8 @@
 //   - the fixed fields of S1 / S2 and of their room-class twins, exactly as get_state_spec_kernel
 //     (simaps_spec.hip) fixes them, with the same levers (GS_SPEC);
 //   - SIMAPS_STATE16 for the element type;
-//   - GS_INTO for the store row: get_state_into_kernel's contract (simaps_store.inc) -- dest[blockIdx.x]
-//     is read first, -1 returns before anything is touched, a row outside [0, capacity) posts
-//     SIMAPS_FAULT_DESCRIPTOR under SIMAPS_K_GET_STATE_INTO and writes nothing, the row's 64-bit
-//     offset goes onto the base pointer once.
+//   - GS_INTO for the store row: get_state_into_kernel's contract (simaps_store.inc), which is store_row's
+//     (get_state_instance.h); the row's 64-bit offset goes onto the base pointer once.
 // The 16-bit kernels also serve simaps_get_state_as: launched with dest == NULL, stack n goes to row
 // n and every fault is posted under SIMAPS_K_GET_STATE, as get_state_bf16_kernel / get_state_f16_kernel
 // post it (one kernel for both launches: half the instances to build; the branch is on a kernel
@@ -30,6 +28,7 @@
 #define GS_ROOM_W RW
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
+#include "get_state_instance.h"
 #include "spec_store.h"
 
 #if SIMAPS_STORE_DTYPE == 0
@@ -57,37 +56,16 @@ __global__ void __launch_bounds__(NT) GSS_KERNEL(
     const float *__restrict__ overhead, GSS_ELEM *__restrict__ state, int64_t capacity,
     const int64_t *__restrict__ dest, int C, unsigned *fault)
 {
-    // the workgroup's row of the store: one value per workgroup, read before anything else
+    // the workgroup's row of the store, read before anything else (store_row: get_state_instance.h)
 #ifdef GSS_PLAIN
     int64_t into_row = blockIdx.x;  // (simaps_get_state_as: no dest, stack n at row n)
-    if (dest) {
-        into_row = dest[blockIdx.x];
+    if (dest && !store_row(dest, capacity, fault, into_row)) return;
 #else
-    const int64_t into_row = dest[blockIdx.x];
-    {
+    int64_t into_row;
+    if (!store_row(dest, capacity, fault, into_row)) return;
 #endif
-        if (into_row == -1) return;  // not this agent: nothing written, nothing posted
-        if ((uint64_t)into_row >= (uint64_t)capacity) {
-            // a row outside the store: reported, and the workgroup writes nothing
-            if (threadIdx.x == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GET_STATE_INTO, blockIdx.x);
-            return;
-        }
-    }
     simaps_config cfg = cfg_in;
-    cfg.use_robot_map = 1;
-    cfg.use_distance_to_receptacle_map = 0;
-    cfg.use_shortest_path_to_receptacle_map = REC;
-    cfg.use_shortest_path_map = 1;
-    cfg.use_intention_map = 1;
-    cfg.use_history_map = 0;
-    cfg.use_intention_channels = 0;
-    cfg.layout_chw = 1;
-    if (RH) {  // GS_SPEC_ROOM
-        cfg.H = MH;
-        cfg.W = MW;
-        cfg.room_h = RH;
-        cfg.room_w = RW;
-    }
+    fix_instance_fields<REC, MH, MW, RH, RW>(cfg);  // (RH != 0: GS_SPEC_ROOM)
     const simaps_debug dbg = {};
 #define GS_MIXED 0
 #define GS_INTO 1
@@ -106,19 +84,16 @@ using spec_store_kernel_t = void (*)(simaps_config, Geometry, const simaps_agent
 }  // namespace
 
 namespace simaps_spec_store {
-void GSS_LAUNCH(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, GSS_ELEM *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                hipStream_t stream)
+void GSS_LAUNCH(int id, const simaps::GetStateLaunch &L)
 {
     spec_store_kernel_t k = id == SIMAPS_SPEC_S1 ? GSS_KERNEL<1> : GSS_KERNEL<0>;
     // the room-class twin of S1 / S2 where cfg's shape matches a class exactly (spec.h)
-    if (simaps_spec::room_class_of(cfg) == SIMAPS_ROOM_SMALL) {
+    if (simaps_spec::room_class_of(*L.cfg) == SIMAPS_ROOM_SMALL) {
         constexpr int MH = SIMAPS_ROOM_SMALL_H, MW = SIMAPS_ROOM_SMALL_W, RH = SIMAPS_ROOM_SMALL_RH, RW = SIMAPS_ROOM_SMALL_RW;
         k = id == SIMAPS_SPEC_S1 ? GSS_KERNEL<1, MH, MW, RH, RW> : GSS_KERNEL<0, MH, MW, RH, RW>;
     }
-    hipLaunchKernelGGL(k, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy, overhead,
-                       store, capacity, dest, C, fault);
+    hipLaunchKernelGGL(k, dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo, L.agents, L.envs, L.robots, L.paths,
+                       L.occupancy, L.overhead, (GSS_ELEM *)L.state, L.capacity, L.dest, L.C, L.fault);
 }
 }  // namespace simaps_spec_store
 

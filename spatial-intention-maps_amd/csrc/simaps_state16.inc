@@ -33,12 +33,9 @@ __global__ void __launch_bounds__(NT) GS16_KERNEL(
 }  // namespace
 
 namespace simaps_state16 {
-void GS16_LAUNCH(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                 const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                 const float *overhead, uint16_t *state, int C, const simaps_debug &dbg, unsigned *fault,
-                 hipStream_t stream)
+void GS16_LAUNCH(const simaps::GetStateLaunch &L)
 {
-    hipLaunchKernelGGL(GS16_KERNEL, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy,
-                       overhead, state, C, dbg, fault);
+    hipLaunchKernelGGL(GS16_KERNEL, dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo, L.agents, L.envs, L.robots,
+                       L.paths, L.occupancy, L.overhead, (uint16_t *)L.state, L.C, L.dbg, L.fault);
 }
 }  // namespace simaps_state16

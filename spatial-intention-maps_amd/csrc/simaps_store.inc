@@ -22,6 +22,7 @@
 #endif
 #define SIMAPS_DEVICE_ONLY
 #include "simaps.hip"
+#include "get_state_instance.h"
 #include "store.h"
 
 #if SIMAPS_STORE_DTYPE == 0
@@ -49,14 +50,9 @@ __global__ void __launch_bounds__(NT) GSI_KERNEL(
     const float *__restrict__ overhead, GSI_ELEM *__restrict__ state, int64_t capacity,
     const int64_t *__restrict__ dest, int C, simaps_debug dbg, unsigned *fault)
 {
-    // the workgroup's row of the store: one value per workgroup, read before anything else
-    const int64_t into_row = dest[blockIdx.x];
-    if (into_row == -1) return;  // not this agent: nothing written, nothing posted
-    if ((uint64_t)into_row >= (uint64_t)capacity) {
-        // a row outside the store: reported, and the workgroup writes nothing
-        if (threadIdx.x == 0) post_faults(fault, SIMAPS_FAULT_DESCRIPTOR, SIMAPS_K_GET_STATE_INTO, blockIdx.x);
-        return;
-    }
+    // the workgroup's row of the store, read before anything else (store_row: get_state_instance.h)
+    int64_t into_row;
+    if (!store_row(dest, capacity, fault, into_row)) return;
 #define GS_MIXED 0
 #define GS_INTO 1
 #include "get_state_body.inc"
@@ -90,23 +86,17 @@ __global__ void __launch_bounds__(NT) GSM_KERNEL(
 }  // namespace
 
 namespace simaps_store {
-void GSI_LAUNCH(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, GSI_ELEM *store, int64_t capacity, const int64_t *dest, int C,
-                const simaps_debug &dbg, unsigned *fault, hipStream_t stream)
+void GSI_LAUNCH(const simaps::GetStateLaunch &L)
 {
-    hipLaunchKernelGGL(GSI_KERNEL, dim3(N), dim3(NT), 0, stream, cfg, geo, agents, envs, robots, paths, occupancy,
-                       overhead, store, capacity, dest, C, dbg, fault);
+    hipLaunchKernelGGL(GSI_KERNEL, dim3(L.N), dim3(NT), 0, L.stream, *L.cfg, *L.geo, L.agents, L.envs, L.robots, L.paths,
+                       L.occupancy, L.overhead, (GSI_ELEM *)L.state, L.capacity, L.dest, L.C, L.dbg, L.fault);
 }
 
 #ifdef GSM_KERNEL
-void GSM_LAUNCH(const simaps_mixed::MixedCfgs &mx, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const int32_t *agent_cfg, const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                const uint8_t *occupancy, const int64_t *map_off, const float *overhead, uint16_t *state,
-                const int64_t *out_off, unsigned *fault, hipStream_t stream)
+void GSM_LAUNCH(const simaps_mixed::MixedLaunch &L)
 {
-    hipLaunchKernelGGL(GSM_KERNEL, dim3(N), dim3(NT), 0, stream, mx, geo, agents, agent_cfg, envs, robots, paths,
-                       occupancy, map_off, overhead, state, out_off, fault);
+    hipLaunchKernelGGL(GSM_KERNEL, dim3(L.N), dim3(NT), 0, L.stream, *L.mx, *L.geo, L.agents, L.agent_cfg, L.envs, L.robots,
+                       L.paths, L.occupancy, L.map_off, L.overhead, (uint16_t *)L.state, L.out_off, L.fault);
 }
 #endif
 }  // namespace simaps_store

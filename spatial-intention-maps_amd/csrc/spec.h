@@ -3,7 +3,7 @@
 // adding them cannot change the code the compiler makes of the generic kernel in simaps.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "geom.h"
+#include "get_state_launch.h"
 #include "simaps_spec.h"
 #include "simaps_spec_room.h"
 
@@ -33,12 +33,8 @@ inline bool any_debug(const simaps_debug &d)
     return d.cspace || d.sources || d.dist || d.status || d.rec_cache;
 }
 
-// id: SIMAPS_SPEC_S1 / SIMAPS_SPEC_S2, as instance_of(cfg, false) gave it; the other arguments are
-// get_state_kernel's without the simaps_debug
-void launch_get_state(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                      const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                      const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
-                      hipStream_t stream);
+// id: SIMAPS_SPEC_S1 / SIMAPS_SPEC_S2, as instance_of(cfg, false) gave it; float32, no store
+void launch_get_state(int id, const simaps::GetStateLaunch &L);
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
 // diagnostic builds: the instances' stamp table (simaps_debug_read_stamps reads the table of the
 // kernel that the last get_state launch took)

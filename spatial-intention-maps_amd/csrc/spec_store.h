@@ -5,7 +5,7 @@
 // the compiler makes of any other kernel.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "geom.h"
+#include "get_state_launch.h"
 #include "simaps_spec_store.h"
 #include "spec.h"
 
@@ -21,19 +21,13 @@ inline int instance_as(const simaps_config &c, int /*state_dtype*/, bool /*into*
 }
 
 // id: SIMAPS_SPEC_S1 / SIMAPS_SPEC_S2, as instance_as gave it; the room-class twin is chosen inside
-// (spec.h room_class_of).  store / capacity / dest: get_state_into_kernel's.  The 16-bit launchers
-// take dest == nullptr for simaps_get_state_as: stack n goes to row n of `store` (capacity unused)
-// and faults are posted under SIMAPS_K_GET_STATE.
-void launch_f32(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, float *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                hipStream_t stream);
-void launch_bf16(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                 const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                 const float *overhead, uint16_t *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                 hipStream_t stream);
-void launch_f16(int id, const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, uint16_t *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                hipStream_t stream);
+// (spec.h room_class_of).  One function per element type's unit; only the 16-bit ones take
+// L.dest == nullptr (simaps_get_state_as).
+void launch_f32(int id, const simaps::GetStateLaunch &L);
+void launch_bf16(int id, const simaps::GetStateLaunch &L);
+void launch_f16(int id, const simaps::GetStateLaunch &L);
+inline void launch(int id, const simaps::GetStateLaunch &L)
+{
+    (L.state_dtype == SIMAPS_STATE_F32 ? launch_f32 : L.state_dtype == SIMAPS_STATE_BF16 ? launch_bf16 : launch_f16)(id, L);
+}
 }  // namespace simaps_spec_store

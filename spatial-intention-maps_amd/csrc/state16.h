@@ -4,17 +4,15 @@
 // compiler makes of the float32 kernels in simaps.hip and simaps_mixed.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "geom.h"
+#include "get_state_launch.h"
 #include "simaps.h"
 
 namespace simaps_state16 {
-// state: [N, C, 96, 96] (chw) or [N, 96, 96, C] 16-bit elements; the arguments of get_state_kernel
-void launch_get_state_bf16(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                           const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                           const uint8_t *occupancy, const float *overhead, uint16_t *state, int C,
-                           const simaps_debug &dbg, unsigned *fault, hipStream_t stream);
-void launch_get_state_f16(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                          const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                          const uint8_t *occupancy, const float *overhead, uint16_t *state, int C,
-                          const simaps_debug &dbg, unsigned *fault, hipStream_t stream);
+// one function per element type's unit; L.state_dtype is bf16 or fp16 and L.dest unused (get_state_launch.h)
+void launch_get_state_bf16(const simaps::GetStateLaunch &L);
+void launch_get_state_f16(const simaps::GetStateLaunch &L);
+inline void launch_get_state(const simaps::GetStateLaunch &L)
+{
+    (L.state_dtype == SIMAPS_STATE_BF16 ? launch_get_state_bf16 : launch_get_state_f16)(L);
+}
 }  // namespace simaps_state16

@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
-#include "geom.h"
+#include "get_state_launch.h"
 #include "simaps_state_cache.h"
 #include "spec.h"
 
@@ -32,11 +32,8 @@ inline bool uses_cache(const simaps_config &c, bool any_debug)
            c.room_j0 - WIN_PAD >= 0 && a0 + 144 <= c.W;  // (occ4_ok: W % 4 == 0 in the class)
 }
 
-// get_state_kernel's arguments without the simaps_debug, and the cache
-void launch_get_state(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                      const simaps_env *envs, const simaps_robot *robots, const double *paths,
-                      const uint8_t *occupancy, const float *overhead, float *state, int C, unsigned *fault,
-                      void *cache, int cache_records, hipStream_t stream);
+// float32, no store; L.cache and L.cache_records are set (get_state_launch.h)
+void launch_get_state(const simaps::GetStateLaunch &L);
 #if defined(SIMAPS_PHASE_STAMPS) || defined(SIMAPS_LIGHT_STAMPS)
 int read_stamps(unsigned long long *host_out);  // (as simaps_spec::read_stamps: this unit's table)
 #endif

@@ -5,7 +5,7 @@
 // hit / miss rule are state_cache.h's, unchanged: any cached kernel may hit on any other's record.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "geom.h"
+#include "get_state_launch.h"
 #include "simaps_state_cache_store.h"
 #include "spec_store.h"
 #include "state_cache.h"
@@ -22,19 +22,13 @@ inline bool applies(const simaps_config &c, int state_dtype, bool into, bool any
            c.room_j0 - simaps_state_cache::WIN_PAD >= 0 && a0 + 144 <= c.W;
 }
 
-// simaps_spec_store's launchers (spec_store.h) for instance S1 in the small room class, and the cache.
-// The 16-bit launchers take dest == nullptr for simaps_get_state_as_cached: stack n goes to row n of
-// `store` (capacity unused) and faults are posted under SIMAPS_K_GET_STATE.
-void launch_f32(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, float *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                void *cache, int cache_records, hipStream_t stream);
-void launch_bf16(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                 const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                 const float *overhead, uint16_t *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                 void *cache, int cache_records, hipStream_t stream);
-void launch_f16(const simaps_config &cfg, const simaps::Geometry &geo, int N, const simaps_agent *agents,
-                const simaps_env *envs, const simaps_robot *robots, const double *paths, const uint8_t *occupancy,
-                const float *overhead, uint16_t *store, int64_t capacity, const int64_t *dest, int C, unsigned *fault,
-                void *cache, int cache_records, hipStream_t stream);
+// simaps_spec_store's launchers (spec_store.h) for instance S1 in the small room class, with L.cache and
+// L.cache_records set.  Only the 16-bit ones take L.dest == nullptr (simaps_get_state_as_cached).
+void launch_f32(const simaps::GetStateLaunch &L);
+void launch_bf16(const simaps::GetStateLaunch &L);
+void launch_f16(const simaps::GetStateLaunch &L);
+inline void launch(const simaps::GetStateLaunch &L)
+{
+    (L.state_dtype == SIMAPS_STATE_F32 ? launch_f32 : L.state_dtype == SIMAPS_STATE_BF16 ? launch_bf16 : launch_f16)(L);
+}
 }  // namespace simaps_state_cache_store
